@@ -13,6 +13,12 @@ x 8 aggs) are all_gather'ed and merged with MergePartialResult semantics
 (aggfuncs.go:250-255) — payload is KBs, latency-bound.
 
 Prints ONE JSON line from rank 0 (driver contract).
+
+A plain run sets up, warms up, times the steps and prints the line. The
+legs around the headline figure (CPU-oracle baselines, the embedded Q3 SF100
+leg) run only with --full. --dump-outputs DIR writes what the last timed
+step returned as DIR/<name>.npy (float64) so two builds can be compared
+output for output.
 """
 import argparse
 import ctypes
@@ -36,6 +42,38 @@ HBM_PEAK_GBS = 8000.0  # spec peak (MI355X_MICROARCH.md; measured ceiling ~6290)
 def log(msg):
     if int(os.environ.get("RANK", "0")) == 0:
         print(msg, file=sys.stderr, flush=True)
+
+
+Q1_OUT_NAMES = ["returnflag", "linestatus", "sum_qty", "sum_base_price",
+                "sum_disc_price", "sum_charge", "avg_qty", "avg_price",
+                "avg_disc", "count_order"]
+Q3_OUT_NAMES = ["orderkey", "orderdate", "shippriority", "revenue"]
+
+
+def dump_outputs(dirpath, prefix, names, types, rows):
+    """Write decoded result rows column by column as
+    dirpath/<prefix>_<name>.npy, float64. Numeric columns (ints, packed
+    times, decimals) become a vector, NULL = NaN; string columns become a
+    rows x max-bytes matrix of byte codes, padded with -1, NULL row = NaN."""
+    import numpy as np
+    from tests.gxlib import GX_TYPE_STRING
+    assert len(names) == len(types)
+    os.makedirs(dirpath, exist_ok=True)
+    for c, (name, typ) in enumerate(zip(names, types)):
+        vals = [r[c] for r in rows]
+        if typ == GX_TYPE_STRING:
+            enc = [None if v is None else v.encode() for v in vals]
+            width = max([len(b) for b in enc if b is not None] + [1])
+            arr = np.full((len(enc), width), -1.0, dtype=np.float64)
+            for i, b in enumerate(enc):
+                if b is None:
+                    arr[i, :] = np.nan
+                else:
+                    arr[i, :len(b)] = list(b)
+        else:
+            arr = np.array([np.nan if v is None else float(v) for v in vals],
+                           dtype=np.float64)
+        np.save(os.path.join(dirpath, f"{prefix}_{name}.npy"), arr)
 
 
 def run_cpu_baseline(rows=8_000_000):
@@ -159,6 +197,8 @@ def q3_result(args):
         rows, k = step()
         kms.append(k)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "q3", Q3_OUT_NAMES, out_types, rows)
     total_rows = n_li + n_ord + n_cust
     value = total_rows * args.steps / elapsed
     # probe-kernel roofline: algorithmic bytes per lineitem row on the Q3
@@ -338,10 +378,15 @@ def bench_wide(args):
         step()
     t0 = time.perf_counter()
     kms = []
+    rows = []
     for _ in range(args.steps):
-        _, k = step()
+        rows, k = step()
         kms.append(k)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "wide",
+                     [f"col{c}" for c in range(len(out_types))], out_types,
+                     rows)
     avg_kms = sum(kms) / len(kms)
     value = n / (avg_kms / 1000.0) if avg_kms else 0
     bpr = 170  # same resident lineitem shard as Q1
@@ -798,10 +843,26 @@ def main():
                     default="q1")
     ap.add_argument("--sf", type=int, default=100,
                     help="scale factor for --query q3 (lineitem = 6M x SF)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs around the headline figure: the "
+                         "CPU-oracle baseline and, for q1 on one GPU, the "
+                         "embedded Q3 SF100 leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU-oracle baseline")
     ap.add_argument("--no-q3", action="store_true",
-                    help="skip the embedded Q3 SF100 leg of the default run")
+                    help="with --full: skip the embedded Q3 SF100 leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as "
+                         "DIR/<name>.npy (float64); --query q1, q3 and wide")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.query not in ("q1", "q3", "wide"):
+        ap.error("--dump-outputs: --query %s hands no rows back to the "
+                 "caller" % args.query)
+    if not args.full:
+        args.no_cpu_baseline = True
+        args.no_q3 = True
 
     if args.query == "q3":
         return bench_q3(args)
@@ -908,6 +969,14 @@ def main():
 
     if rank != 0:
         return
+
+    if args.dump_outputs:
+        # group order out of the hash table is not part of the result
+        q1_rows = sorted((k + v for k, v in result.items()),
+                         key=lambda r: tuple(x or "" for x in r[:2]))
+        # merged (N>1) and COMPLETE results share the final schema
+        dump_outputs(args.dump_outputs, "q1", Q1_OUT_NAMES,
+                     [4, 4] + [2] * 7 + [0], q1_rows)
 
     ms_per_step = elapsed / args.steps * 1000.0
     value = (args.rows * n_gpus) * args.steps / elapsed
