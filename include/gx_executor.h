@@ -291,6 +291,12 @@ const char* gx_engine_name(void);
  * row count that passed the filter in the last run. */
 double  gx_last_kernel_ms(gx_exec* ex);
 int64_t gx_last_sel_count(gx_exec* ex);
+/* product engine only, debug (not part of the stable ABI): the hipRTC source
+ * the engine would generate for this plan, and the number of decimal columns
+ * currently served from an int64 units column (fused table + join-agg probe;
+ * 0 while every decimal still reads the 40-byte form). */
+const char* gx_debug_jit_source(gx_exec* ex);
+int32_t gx_debug_dec_units_cols(gx_exec* ex);
 
 /* ---- decimal helpers (each library's own implementation; used by golden
  * vector tests against pkg/types/mydecimal_test.go answers) ---- */

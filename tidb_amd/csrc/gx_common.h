@@ -17,6 +17,11 @@ struct DevCol {
   void* data = nullptr;          // fixed: N*elem; varlen: bytes
   uint8_t* nullBitmap = nullptr; // LSB-first, 1 = NOT NULL; null => no NULLs
   int64_t* offsets = nullptr;    // varlen: N+1
+  // decimal col of a resident table: int64 units at the declared frac, one
+  // per row (NULL rows hold 0). Built once at bind, and only when every
+  // non-NULL row was proven to parse to exactly these units at exactly the
+  // declared frac (gxBuildDecUnits); null => read the 40 B form.
+  int64_t* units = nullptr;
   int32_t elemSize = 8;          // -1 varlen
   int32_t type = 0;              // gx type
   int32_t frac = 0;
@@ -117,6 +122,9 @@ enum FetchKind : int32_t {
   FETCH_8B_CHAR2 = 4, // x = 8-byte element; y = 1-2 dense char(1) cols packed
                       // (plain kernel: prefetches group chars with the row)
   FETCH_CHAR2 = 5,    // y = 1-2 dense char(1) cols packed; x unused
+  FETCH_UNITS8 = 6,   // 8 bytes at units[row]: x = int64 units at the column's
+                      // declared frac, y = 0 (a FETCH_DEC16 slot rewritten in
+                      // place at bind for a column whose units were proven)
 };
 
 struct FetchDesc {
@@ -596,6 +604,12 @@ int gxLaunchFusedAgg(const FusedQueryDesc& desc, const FusedQueryDesc* devDesc,
                      void* stream, int skipInit = 0);
 int gxLaunchMemset(void* p, int v, size_t n, void* stream);
 int gxFusedGrid(int64_t rows);
+// one streaming pass over a 40 B decimal column: out[row] = int64 units at
+// declaredFrac (0 for NULL rows). *flag becomes nonzero unless EVERY non-NULL
+// row has a valid header, digitsFrac == declaredFrac exactly, and units that
+// fit int64 -- the proof that lets the scan serve the column from `out`.
+int gxBuildDecUnits(const DevCol& col, int64_t nRows, int declaredFrac,
+                    int64_t* out, uint32_t* flag, void* stream);
 int gxLaunchInitTable(GroupSlot* table, int64_t nSlots, void* stream);
 int gxDumpDesc(const FusedQueryDesc* devDesc, void* stream);
 

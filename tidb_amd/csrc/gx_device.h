@@ -288,6 +288,9 @@ __device__ __attribute__((always_inline)) inline void fetchRow(const DevTable& t
       const uint8_t* p = (const uint8_t*)c.data + row * 40;
       v.x = *gptr<uint64_t>(p);
       v.y = *gptr<uint64_t>(p + 8);
+    } else if (fd.kind == FETCH_UNITS8) {
+      v.x = (uint64_t)gptr<int64_t>(c.units)[row];
+      v.y = 0;
     } else {  // FETCH_OFFSETS
       v.x = (uint64_t)gptr<int64_t>(c.offsets)[row];
       v.y = (uint64_t)gptr<int64_t>(c.offsets)[row + 1];

@@ -251,6 +251,9 @@ struct gx_exec {
   // output into desc.table, then the fused aggregation runs over it
   bool aggOverJoin = false;
   bool fusedBindDone = false;
+  // decimal columns currently served from DevCol::units (buildDecUnits):
+  // fused table / join-agg probe table
+  int decUnitsFused = 0, decUnitsJa = 0;
   // standalone Selection (compact survivors of a CNF over one source)
   bool isSelect = false;
   JoinStage selStage;  // probe side only (srcP); hj.post = the CNF
@@ -2851,6 +2854,90 @@ static int32_t ensureWideKeyStore(gx_exec* ex) {
   return GX_OK;
 }
 
+static int64_t hbmBudgetBytes();
+
+// resident bytes of a materialized table by schema (the out-of-core
+// decisions' arithmetic: 40 B decimal, 8+1 B char(1) string, 8 B otherwise)
+static int64_t tableSchemaBytes(const gxp::DevTable& tab) {
+  int64_t rb = 0;
+  for (int c = 0; c < tab.nCols; c++) {
+    int t = tab.cols[c].type;
+    rb += t == GX_TYPE_DECIMAL ? 40 : (t == GX_TYPE_STRING ? 9 : 8);
+  }
+  return rb * tab.nRows;
+}
+
+// Decimal units columns. `tab` is a RESIDENT source table
+// (generator or bound chunks: filled once, re-read by every later open), so
+// the 40 B -> int64 conversion the scan repeats per row per query is done
+// here once. Each listed column gets an 8 B/row buffer filled by
+// gxBuildDecUnits; a column whose proof fails keeps units == nullptr and its
+// 40 B path. Never an error: a short budget, a failed allocation or a failed
+// launch all leave the query exactly where it was. Returns the number of
+// columns now served from units.
+static int buildDecUnits(gx_exec* ex, gxp::DevTable& tab,
+                         const std::vector<int>& cols, int64_t residentBytes) {
+  if (cols.empty() || tab.nRows <= 0 || getenv("GX_NO_DEC_UNITS")) return 0;
+  const bool dbg = getenv("GX_DEBUG") != nullptr;
+  // GX_HBM_BUDGET caps the executor's whole footprint, so the tables already
+  // resident count against it; the default budget is a share of what is
+  // free NOW, i.e. after materialization
+  int64_t budget = hbmBudgetBytes();
+  if (getenv("GX_HBM_BUDGET")) budget -= residentBytes;
+  const int64_t need = (int64_t)cols.size() * tab.nRows * 8;
+  if (need > budget) {
+    if (dbg)
+      fprintf(stderr, "[gx] dec units: %lld B over budget %lld B, not built\n",
+              (long long)need, (long long)budget);
+    return 0;
+  }
+  uint32_t* flags = (uint32_t*)devAllocP(ex, cols.size() * 4);
+  if (!flags) return 0;
+  std::vector<int64_t*> bufs(cols.size(), nullptr);
+  std::vector<hipEvent_t> evs(cols.size() + 1, nullptr);
+  bool ok = hipMemsetAsync(flags, 0, cols.size() * 4, ex->stream) == hipSuccess;
+  for (size_t i = 0; i < cols.size() && ok; i++) {
+    bufs[i] = (int64_t*)devAllocP(ex, (size_t)tab.nRows * 8);
+    ok = bufs[i] != nullptr;
+  }
+  if (!ok) (void)hipGetLastError();  // a failed hipMalloc is not our error
+  if (ok && dbg) {
+    for (auto& e : evs) hipEventCreate(&e);
+    hipEventRecord(evs[0], ex->stream);
+  }
+  for (size_t i = 0; i < cols.size() && ok; i++) {
+    const gxp::DevCol& c = tab.cols[cols[i]];
+    ok = gxp::gxBuildDecUnits(c, tab.nRows, c.frac, bufs[i], flags + i,
+                              ex->stream) == 0;
+    if (ok && dbg) hipEventRecord(evs[i + 1], ex->stream);
+  }
+  std::vector<uint32_t> hflags(cols.size(), 1u);
+  ok = ok && hipStreamSynchronize(ex->stream) == hipSuccess &&
+       hipMemcpy(hflags.data(), flags, cols.size() * 4,
+                 hipMemcpyDeviceToHost) == hipSuccess;
+  int built = 0;
+  for (size_t i = 0; i < cols.size(); i++) {
+    bool proven = ok && hflags[i] == 0;
+    if (dbg && ok) {
+      float ms = 0;
+      hipEventElapsedTime(&ms, evs[i], evs[i + 1]);
+      fprintf(stderr, "[gx] dec units col %d frac %d: %s, build %.3f ms\n",
+              cols[i], tab.cols[cols[i]].frac,
+              proven ? "compacted" : "kept 40 B (proof failed)", ms);
+    }
+    if (proven) {
+      tab.cols[cols[i]].units = bufs[i];
+      built++;
+    } else if (bufs[i]) {
+      devFreeP(ex, bufs[i]);
+    }
+  }
+  for (auto& e : evs)
+    if (e) hipEventDestroy(e);
+  devFreeP(ex, flags);
+  return built;
+}
+
 // bind-time fixups + result buffers for the fused aggregation, over whatever
 // filled desc.table (a bound/generated source, or a materialized join
 // output). Idempotent (fetch slots must not be re-assigned on re-open).
@@ -2976,6 +3063,26 @@ static int32_t finalizeFusedBind(gx_exec* ex) {
     if (getenv("GX_DEBUG"))
       fprintf(stderr, "[gx] useGlds=%d tileBytes=%d nFetch=%d\n", d.useGlds,
               d.tileBytes, d.nFetch);
+  }
+  // decimal units columns: the fetch plan is final, so every FETCH_DEC16
+  // slot (VM loads -- decimal group keys read those registers -- and decimal
+  // predicates) names a consumed decimal column. Only for a table a source
+  // binding filled: streamed slices and join outputs are re-made every run
+  // (the conversion would be a new pass each time), and the opt-in glds
+  // variant stages the 40 B form.
+  ex->decUnitsFused = 0;
+  if (!ex->aggOverJoin && !ex->fusedStreamed && !ex->desc.useGlds) {
+    gxp::FusedQueryDesc& d = ex->desc;
+    std::vector<int> cols;
+    for (int f = 0; f < d.nFetch; f++)
+      if (d.fetch[f].kind == gxp::FETCH_DEC16 &&
+          std::find(cols.begin(), cols.end(), d.fetch[f].col) == cols.end())
+        cols.push_back(d.fetch[f].col);
+    ex->decUnitsFused = buildDecUnits(ex, tab, cols, tableSchemaBytes(tab));
+    // proven columns: rewrite the slot IN PLACE (slot indices never move)
+    for (int f = 0; f < d.nFetch; f++)
+      if (d.fetch[f].kind == gxp::FETCH_DEC16 && tab.cols[d.fetch[f].col].units)
+        d.fetch[f].kind = gxp::FETCH_UNITS8;
   }
   ex->fusedBindDone = true;
   ex->deviceReady = true;
@@ -3917,6 +4024,20 @@ static int32_t runJoinAgg(gx_exec* ex) {
       return GX_ERR_INTERNAL;
     }
     ja.errorFlag = ex->devErr;
+    // the probe table is resident across opens: serve the decimal columns
+    // its value VM loads from units columns (the build tables carry no
+    // decimals on this path)
+    {
+      std::vector<int> cols;
+      for (int i = 0; i < ja.nIns; i++)
+        if (ja.ins[i].op == gxp::VM_LOAD_DEC &&
+            std::find(cols.begin(), cols.end(), ja.ins[i].a) == cols.end())
+          cols.push_back(ja.ins[i].a);
+      ex->decUnitsJa = buildDecUnits(
+          ex, ja.probe, cols,
+          tableSchemaBytes(ja.build0) + tableSchemaBytes(ja.build1) +
+              tableSchemaBytes(ja.probe));
+    }
     ex->deviceReady = true;
   }
   HIP_OK(ex, hipMemsetAsync(ex->devErr, 0, 4, ex->stream));
@@ -6745,6 +6866,12 @@ const char* gx_debug_jit_source(gx_exec* ex) {
   if (!ex) return "";
   s = gxjit::generateSource(ex->desc);
   return s.c_str();
+}
+
+// debug: decimal columns currently served from an int64 units column (fused
+// table + join-agg probe); 0 when every decimal still reads the 40 B form
+int32_t gx_debug_dec_units_cols(gx_exec* ex) {
+  return ex ? ex->decUnitsFused + ex->decUnitsJa : 0;
 }
 
 double gx_last_kernel_ms(gx_exec* ex) { return ex ? ex->lastKernelMs : 0; }

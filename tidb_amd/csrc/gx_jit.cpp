@@ -94,6 +94,11 @@ static void emitRowPipe(std::ostringstream& s, const FusedQueryDesc& d) {
     } else if (pd.kind == gxp::PRED_I64_CMP_CONST) {
       s << "  if (!((int64_t)raw.get(" << pd.slot << ").x " << cmpOp(pd.cmp)
         << " (int64_t)" << (int64_t)pd.constU64 << "LL)) return true;\n";
+    } else if (pd.kind == gxp::PRED_DEC_CMP_CONST && pd.slot >= 0 &&
+               d.fetch[pd.slot].kind == gxp::FETCH_UNITS8) {
+      // proven column: the slot holds int64 units at the const's scale
+      s << "  if (!((int64_t)raw.get(" << pd.slot << ").x " << cmpOp(pd.cmp)
+        << " (int64_t)" << (int64_t)pd.constU64 << "LL)) return true;\n";
     } else if (pd.kind == gxp::PRED_DEC_CMP_CONST) {
       s << "  { T u; int sc;\n"
            "    if (!loadDecimalUnits<WIDE>((const uint8_t*)d.table.cols["
@@ -120,6 +125,13 @@ static void emitRowPipe(std::ostringstream& s, const FusedQueryDesc& d) {
         if (c.hasNulls)
           s << "  " << nv << " = colIsNull(d.table.cols[" << ins.a
             << "], row);\n";
+        if (d.fetch[ins.c].kind == gxp::FETCH_UNITS8) {
+          // proven column: units at scale ins.b straight from the slot
+          s << "  if (!" << nv << ") " << v
+            << " = VT<WIDE>::fromI64((int64_t)raw.get(" << ins.c
+            << ").x, nullptr);\n";
+          break;
+        }
         s << "  if (!" << nv << ") { int sc;\n"
           << "    if (!parseDecimalRaw<WIDE>(raw.get(" << ins.c << "), &" << v
           << ", &sc, d.errorFlag, " << ins.b << ", " << d.insP10[i] << "LL, "
@@ -421,6 +433,9 @@ static void emitFetch(std::ostringstream& s, const FusedQueryDesc& d) {
         << "].data + row * 40;\n"
         << "    " << m << ".x = *gptr<uint64_t>(p); " << m
         << ".y = *gptr<uint64_t>(p + 8); }\n";
+    } else if (fd.kind == gxp::FETCH_UNITS8) {
+      s << "  " << m << ".x = (uint64_t)gptr<int64_t>(t.cols[" << fd.col
+        << "].units)[row]; " << m << ".y = 0;\n";
     } else {  // FETCH_OFFSETS
       s << "  " << m << ".x = (uint64_t)gptr<int64_t>(t.cols[" << fd.col
         << "].offsets)[row]; " << m << ".y = (uint64_t)gptr<int64_t>(t.cols["
@@ -642,6 +657,13 @@ static void emitJaVm(std::ostringstream& s, const JoinAggDesc& d) {
         if (c.hasNulls)
           s << "    " << nv << " = colIsNull(d.probe.cols[" << ins.a
             << "], row);\n";
+        if (c.units) {
+          // proven column: int64 units at the declared frac (= ins.b)
+          s << "    if (!" << nv << ") " << v
+            << " = VT<WIDE>::fromI64(gptr<int64_t>(d.probe.cols[" << ins.a
+            << "].units)[row], nullptr);\n";
+          break;
+        }
         s << "    if (!" << nv << ") { int sc;\n";
         if (ins.c >= 0)
           s << "      if (!parseDecimalRaw<WIDE>(raw.get(" << ins.c << "), &"

@@ -161,8 +161,11 @@ __device__ __attribute__((always_inline)) inline bool processRow(const FusedQuer
     if (pd.kind == PRED_DEC_CMP_CONST) {
       typename VT<WIDE>::T u;
       int sc;
-      if (!loadDecimalUnits<WIDE>((const uint8_t*)c.data + row * 40, &u, &sc,
-                                  d.errorFlag)) {
+      if (pd.slot >= 0 && d.fetch[pd.slot].kind == FETCH_UNITS8) {
+        // proven column: the slot already holds the units at the column frac
+        u = VT<WIDE>::fromI64((int64_t)raw.get(pd.slot).x, nullptr);
+      } else if (!loadDecimalUnits<WIDE>((const uint8_t*)c.data + row * 40, &u,
+                                         &sc, d.errorFlag)) {
         hardFail = true;
         return false;
       }
@@ -197,7 +200,10 @@ __device__ __attribute__((always_inline)) inline bool processRow(const FusedQuer
         const DevCol& c = d.table.cols[ins.a];
         bool nul = colIsNull(c, row);
         typename VT<WIDE>::T v = VT<WIDE>::zero();
-        if (!nul) {
+        if (!nul && d.fetch[ins.c].kind == FETCH_UNITS8) {
+          // proven column: units at scale ins.b, sign-extended when WIDE
+          v = VT<WIDE>::fromI64((int64_t)raw.get(ins.c).x, nullptr);
+        } else if (!nul) {
           int sc;
           if (!parseDecimalRaw<WIDE>(raw.get(ins.c), &v, &sc, d.errorFlag,
                                      ins.b, d.insP10[i], d.insMagic[i])) {
@@ -1023,7 +1029,10 @@ __global__ void jaProbeKernel(const JoinAggDesc* __restrict__ dp) {
           const DevCol& c = d.probe.cols[ins.a];
           bool nul = colIsNull(c, row);
           typename VT<WIDE>::T v = VT<WIDE>::zero();
-          if (!nul) {
+          if (!nul && c.units) {
+            // proven column: int64 units at the declared frac (= ins.b)
+            v = VT<WIDE>::fromI64(gptr<int64_t>(c.units)[row], nullptr);
+          } else if (!nul) {
             int sc;
             bool okp = ins.c >= 0
                 ? parseDecimalRaw<WIDE>(raw.get(ins.c), &v, &sc, d.errorFlag)
@@ -1842,6 +1851,67 @@ int gxFusedGrid(int64_t rows) {
   if (grid > 2048) grid = 2048;
   if (grid < 1) grid = 1;
   return grid;
+}
+
+// ---- decimal units column (DevCol::units) ----
+// One pass over a resident 40 B decimal column: the same two 8-byte loads as
+// loadDecimalUnits, the same arithmetic as the narrow parseDecimalRaw, one
+// coalesced 8 B store per lane. A row that is not exactly servable (bad
+// header, digitsFrac != declaredFrac, units beyond int64) only raises the
+// flag -- no error moves to bind time; the engine drops the buffer and the
+// column keeps its FETCH_DEC16 path with every error surface where it was.
+__launch_bounds__(256)
+__global__ void buildDecUnitsKernel(DevCol col, int64_t nRows, int declaredFrac,
+                                    int64_t* __restrict__ out, uint32_t* flag) {
+  const int64_t p10v = kP10(declaredFrac);
+  const uint64_t magic = kDivMagic(9 - declaredFrac);
+  bool bad = false;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       row < nRows; row += stride) {
+    int64_t units = 0;
+    if (!colIsNull(col, row)) {
+      const uint8_t* p = (const uint8_t*)col.data + row * 40;
+      uint64_t w0 = *gptr<uint64_t>(p);
+      uint64_t w1 = *gptr<uint64_t>(p + 8);
+      uint32_t hdr = (uint32_t)w0;
+      int digitsInt = (int)(int8_t)(hdr & 0xFF);
+      int digitsFrac = (int)(int8_t)((hdr >> 8) & 0xFF);
+      bool neg = ((hdr >> 24) & 0xFF) != 0;
+      if (digitsInt < 0 || digitsInt > 18 || digitsFrac != declaredFrac) {
+        bad = true;
+      } else {
+        int wordsInt = (digitsInt + 8) / 9;
+        int32_t word0 = (int32_t)(uint32_t)(w0 >> 32);
+        int32_t word1 = (int32_t)(uint32_t)w1;
+        uint32_t word2 = (uint32_t)(w1 >> 32);
+        int64_t ip = 0;
+        if (wordsInt == 1) ip = word0;
+        else if (wordsInt == 2) ip = (int64_t)word0 * 1000000000 + word1;
+        uint32_t fw = wordsInt == 0 ? (uint32_t)word0
+                                    : (wordsInt == 1 ? (uint32_t)word1 : word2);
+        int64_t fr = declaredFrac > 0
+                         ? (int64_t)(((unsigned __int128)fw * magic) >> 62)
+                         : 0;
+        bool ovf = __builtin_mul_overflow(ip, p10v, &units);
+        ovf |= __builtin_add_overflow(units, fr, &units);
+        if (ovf) { bad = true; units = 0; }
+        else if (neg) units = -units;
+      }
+    }
+    out[row] = units;
+  }
+  // at most one atomic per failing wave
+  if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
+}
+
+int gxBuildDecUnits(const DevCol& col, int64_t nRows, int declaredFrac,
+                    int64_t* out, uint32_t* flag, void* stream) {
+  if (declaredFrac < 0 || declaredFrac > 9) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(buildDecUnitsKernel, dim3(gxFusedGrid(nRows)), dim3(256),
+                     0, (hipStream_t)stream, col, nRows, declaredFrac, out,
+                     flag);
+  return (int)hipGetLastError();
 }
 
 int gxLaunchInitTable(GroupSlot* table, int64_t nSlots, void* stream) {
