@@ -143,7 +143,24 @@ enum {
    * Supported on the standalone Selection and inner-join other-condition
    * paths this round (a NULL leaf behaves as FALSE, which matches
    * VecEvalBool's NULL-rejects within both OR and AND). */
-  GX_F_OR = 53
+  GX_F_OR = 53,
+  /* general LIKE / NOT LIKE (builtinLikeSig over
+   * stringutil.CompilePatternBinary / DoMatchBinary): args (string COLUMN,
+   * const string pattern [, const i64 escape byte, default 92 '\']).
+   * Binary collation, byte semantics: `%` matches any run of bytes
+   * (including none), `_` exactly one BYTE, escape + (escape | _ | %) that
+   * byte literally, any other or a trailing escape is itself a literal;
+   * case-sensitive, the whole string must match, no PAD SPACE trimming.
+   * Result i64 0/1, NULL when the string is NULL. NOT_LIKE is the
+   * UnaryNot(Like) composition: the negation, NULL staying NULL. Valid as a
+   * Selection conjunct or OR leaf at every filter site (NULL rejects the
+   * row) and in value context (Projection and fused-aggregate expressions;
+   * not in the join-aggregate pipeline's probe expression). Limits: the
+   * pattern compiles to at most 32 elements (after `%%` collapsing) and is
+   * constant, the first argument is a column, the escape lies in 0..255,
+   * at most 4 distinct value-context patterns per operator -- anything else
+   * is GX_ERR_INVALID at plan compile. */
+  GX_F_LIKE = 54, GX_F_NOT_LIKE = 55
 };
 
 /* ---- aggregate function codes (pkg/executor/aggfuncs) ---- */
@@ -320,6 +337,19 @@ int32_t gx_dec_to_hash_key(const uint8_t in[40], uint8_t* out, int32_t* out_len)
 int32_t gx_dec_from_i64(int64_t v, uint8_t out[40]);
 int32_t gx_dec_shift(const uint8_t in[40], int32_t shift, uint8_t out[40]);
 int32_t gx_dec_result_frac(const uint8_t dec40[40]);
+
+/* ---- LIKE helpers (host side, no GPU needed) ----
+ * gx_like_compile: compile a pattern to (char, type) elements, type 0 =
+ * match this byte, 1 = any one byte, 2 = any run. Returns the element count,
+ * or a negative status when the pattern needs more than `cap` elements or
+ * the escape is outside 0..255.
+ * gx_like_match: 1 iff s matches the pattern, else 0 (negative status when
+ * the pattern exceeds the engine's 32-element limit); runs the same matcher
+ * source as the device kernels. */
+int32_t gx_like_compile(const uint8_t* pat, int32_t len, int32_t escape,
+                        uint8_t* out_chars, uint8_t* out_types, int32_t cap);
+int32_t gx_like_match(const uint8_t* pat, int32_t plen, int32_t escape,
+                      const uint8_t* s, int32_t slen);
 
 /* ---- time helpers (packed CoreTime, core_time.go:25 / time.go:233-265) ---- */
 uint64_t gx_time_from_date(int32_t year, int32_t month, int32_t day);

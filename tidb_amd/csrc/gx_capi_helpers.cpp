@@ -5,6 +5,7 @@
 
 #include "../../include/gx_executor.h"
 #include "gx_decimal.h"
+#include "gx_like.h"
 
 using gxp::MyDecimal;
 
@@ -13,6 +14,19 @@ static inline const MyDecimal* D(const uint8_t* p) {
 }
 
 extern "C" {
+
+int32_t gx_like_compile(const uint8_t* pat, int32_t len, int32_t escape,
+                        uint8_t* out_chars, uint8_t* out_types, int32_t cap) {
+  int32_t n = gxp::likeCompile(pat, len, escape, out_chars, out_types, cap);
+  return n < 0 ? GX_ERR_INVALID : n;
+}
+int32_t gx_like_match(const uint8_t* pat, int32_t plen, int32_t escape,
+                      const uint8_t* s, int32_t slen) {
+  gxp::LikePat lp;
+  if (gxp::likeCompilePat(pat, plen, escape, &lp) < 0 || slen < 0)
+    return GX_ERR_INVALID;
+  return gxp::likeMatch(lp.chars, lp.types, lp.n, s, 0, slen) ? 1 : 0;
+}
 
 int32_t gx_dec_from_string(const char* s, int32_t len, uint8_t out40[40]) {
   MyDecimal d;

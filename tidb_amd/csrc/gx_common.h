@@ -10,6 +10,8 @@
 
 #include <cstdint>
 
+#include "gx_like.h"
+
 namespace gxp {
 
 // ---- device column (reference chunk.Column layout resident in HBM) ----
@@ -74,6 +76,9 @@ enum VmOp : int32_t {
                          // (GX_F_LT..GX_F_NE); NULL if either is NULL
   VM_IF = 16,            // dst <- cond(a) truthy ? b : c (builtinIfSig;
                          // NULL cond counts false; branch scales aligned)
+  VM_LIKE = 17,          // dst <- string column a LIKE likePats[b] as i64
+                         // 0/1, negated when c != 0 (NOT LIKE); NULL if the
+                         // string is NULL (offsets load at use)
 };
 
 struct VmIns {
@@ -87,6 +92,7 @@ struct VmIns {
 constexpr int kMaxVmIns = 48;
 constexpr int kMaxVmRegs = 14;
 constexpr int kMaxVmConsts = 16;
+constexpr int kMaxLikePats = 4;  // distinct value-context LIKE patterns
 
 // ---- filter (CNF of simple predicates; Q1-class) ----
 enum PredKind : int32_t {
@@ -101,10 +107,12 @@ struct PredDesc {
   int32_t col;
   int32_t cmp;        // GX_F_LT..GX_F_NE
   int32_t slot;       // raw fetch slot (TIME/I64 preds; -1 = load at use)
-  uint64_t constU64;  // time value or i64/units bits
+  uint64_t constU64;  // time value or i64/units bits; PRED_STR_LIKE: the
+                      // 2-bit element types of the compiled pattern
   // string predicates (PRED_STR_EQ_CONST / PRED_STR_LIKE_PREFIX): the
-  // constant lives inline so every conjunct can carry its own
-  uint8_t strC[16] = {0};
+  // constant lives inline so every conjunct can carry its own.
+  // PRED_STR_LIKE: the compiled pattern's element chars / element count
+  uint8_t strC[kLikeMaxElems] = {0};
   int32_t strCLen = 0;
 };
 
@@ -287,6 +295,9 @@ struct FusedQueryDesc {
   // consumed column carries NULLs.
   int32_t useGlds = 0;
   int32_t tileBytes = 0;  // per-tile LDS bytes (sum of stream slots, 16-aligned)
+  // VM_LIKE pattern table (value-context LIKE)
+  LikePat likePats[kMaxLikePats];
+  int32_t nLikePats = 0;
 };
 
 // ---- join-aggregate pipeline (TPC-H Q3 class) ----
@@ -373,6 +384,11 @@ struct JoinAggDesc {
 
 enum { PRED_STR_EQ_CONST = 3 };  // extra PredKind for the join path
 enum { PRED_STR_LIKE_PREFIX = 6 };  // LIKE 'abc%' fast path (builtinLikeSig)
+enum { PRED_STR_LIKE = 8 };  // general LIKE / NOT LIKE (gx_like.h): the
+                             // compiled pattern lives in the PredDesc
+                             // (strC, strCLen, constU64); cmp EQ = LIKE,
+                             // NE = NOT LIKE; the strConst arguments of
+                             // evalSimplePred are ignored
 enum { PRED_IS_NULL = 7 };  // IS [NOT] NULL (builtin*IsNullSig: result is
                             // the null bit itself, never NULL; cmp EQ = IS
                             // NULL, NE = IS NOT NULL; any column type)
@@ -560,6 +576,8 @@ struct ProjDesc {
   int32_t wide = 0;
   StrProg sprog[kMaxCols];
   int32_t nSprog = 0;
+  LikePat likePats[kMaxLikePats];  // VM_LIKE pattern table
+  int32_t nLikePats = 0;
 };
 
 int gxProject(const ProjDesc* devDesc, const ProjDesc& h, void* stream);

@@ -718,7 +718,27 @@ __device__ inline bool evalSimplePred(const DevTable& tab, const PredDesc& pd,
       if (p[st + j] != strConst[j]) return false;
     return true;
   }
+  if (pd.kind == PRED_STR_LIKE) {
+    // general LIKE / NOT LIKE: the compiled pattern rides in the PredDesc
+    // (strConst is not consulted); no pad trimming
+    int64_t st, en;
+    if (c.denseOffsets) { st = row; en = row + 1; }
+    else { st = gptr<int64_t>(c.offsets)[row]; en = gptr<int64_t>(c.offsets)[row + 1]; }
+    bool m = likeMatch(pd.strC, pd.constU64, pd.strCLen, gptr<uint8_t>(c.data),
+                       st, en);
+    return m == (pd.cmp == 4 /*GX_F_EQ*/);
+  }
   return false;
+}
+
+// value-context LIKE (VM_LIKE): match of string column c at `row` against a
+// pattern-table entry; the caller has already handled NULL
+__device__ inline bool likeColMatch(const DevCol& c, const LikePat& lp,
+                                    int64_t row) {
+  int64_t st, en;
+  if (c.denseOffsets) { st = row; en = row + 1; }
+  else { st = gptr<int64_t>(c.offsets)[row]; en = gptr<int64_t>(c.offsets)[row + 1]; }
+  return likeMatch(lp.chars, lp.types, lp.n, gptr<uint8_t>(c.data), st, en);
 }
 
 // atomic int128 + count accumulation into a slot (LDS or global)

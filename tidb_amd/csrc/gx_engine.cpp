@@ -139,6 +139,9 @@ struct gx_exec {
   bool isFinalHost = false;
   bool isBareSource = false;
   bool isJoinAgg = false;
+  // the join-aggregate compile met a value-context LIKE: a plan error, not a
+  // reason to fall back to aggregation over materialized joined rows
+  bool jaLikeRejected = false;
   int aggRoot = -1;  // the HASHAGG node the fused kernel implements
   // DISTINCT rewrite (aggFuncDesc.HasDistinct): the device kernel groups by
   // (orig keys..., arg) — the dedup — and the decode folds back to the orig
@@ -422,6 +425,65 @@ static void beginRun(gx_exec* ex) {
 
 // ---------------- plan compilation ----------------
 
+// general LIKE / NOT LIKE call (GX_F_LIKE / GX_F_NOT_LIKE): args are
+// (string COLUMN, const string pattern [, const i64 escape byte]). Validates
+// them against the schema the call runs over and compiles the pattern
+// (gx_like.h). colBase = plan colref index of that schema's first column.
+static bool compileLikeCall(gx_exec* ex, const PExpr& e,
+                            const std::vector<int>& colTypes, int colBase,
+                            int* colOut, gxp::LikePat* out) {
+  if (e.args.size() != 2 && e.args.size() != 3) {
+    ex->err = "LIKE takes (string column, const pattern [, const escape])";
+    return false;
+  }
+  const PExpr& col = ex->plan.exprs[e.args[0]];
+  const PExpr& pat = ex->plan.exprs[e.args[1]];
+  int c = col.colIdx - colBase;
+  if (col.kind != EK_COLREF || c < 0 || c >= (int)colTypes.size() ||
+      colTypes[c] != GX_TYPE_STRING) {
+    ex->err = "device LIKE: the first argument must be a string column";
+    return false;
+  }
+  if (pat.kind != EK_CONST || pat.retType != GX_TYPE_STRING) {
+    ex->err = "device LIKE: the pattern must be a string constant";
+    return false;
+  }
+  int64_t esc = 92;
+  if (e.args.size() == 3) {
+    const PExpr& ee = ex->plan.exprs[e.args[2]];
+    if (ee.kind != EK_CONST || ee.retType != GX_TYPE_I64 || ee.constI64 < 0 ||
+        ee.constI64 > 255) {
+      ex->err = "device LIKE: the escape must be a constant byte 0..255";
+      return false;
+    }
+    esc = ee.constI64;
+  }
+  int32_t n = gxp::likeCompilePat((const uint8_t*)pat.constStr.data(),
+                                  (int32_t)pat.constStr.size(), (int32_t)esc,
+                                  out);
+  if (n < 0) {
+    ex->err = "device LIKE: the pattern compiles to more than 32 elements";
+    return false;
+  }
+  *colOut = c;
+  return true;
+}
+
+// value-context LIKE: intern the compiled pattern in a VM_LIKE pattern table
+static int internLikePat(gx_exec* ex, gxp::LikePat* tab, int32_t* nTab,
+                         const gxp::LikePat& lp) {
+  for (int i = 0; i < *nTab; i++)
+    if (tab[i].n == lp.n && tab[i].types == lp.types &&
+        std::memcmp(tab[i].chars, lp.chars, sizeof lp.chars) == 0)
+      return i;
+  if (*nTab >= gxp::kMaxLikePats) {
+    ex->err = "more than 4 distinct LIKE patterns in value context";
+    return -1;
+  }
+  tab[*nTab] = lp;
+  return (*nTab)++;
+}
+
 // compile expression exprId (over SOURCE columns) into the VM; returns reg or
 // -1 on error. *scaleOut = static scale of the value.
 static int compileExpr(gx_exec* ex, int exprId, int* scaleOut) {
@@ -560,6 +622,20 @@ static int compileExpr(gx_exec* ex, int exprId, int* scaleOut) {
           return -1;
         }
         reg = emit(gxp::VM_STRLEN, allocRegFresh(), col, 0);
+        *scaleOut = 0;
+        break;
+      }
+      if (e.func == GX_F_LIKE || e.func == GX_F_NOT_LIKE) {
+        // LIKE in value context: i64 0/1, NULL when the string is NULL
+        std::vector<int> types(d.table.nCols);
+        for (int c = 0; c < d.table.nCols; c++) types[c] = d.table.cols[c].type;
+        gxp::LikePat lp;
+        int col;
+        if (!compileLikeCall(ex, e, types, 0, &col, &lp)) return -1;
+        int pi = internLikePat(ex, d.likePats, &d.nLikePats, lp);
+        if (pi < 0) return -1;
+        reg = emit(gxp::VM_LIKE, allocReg(), col, pi);
+        if (reg >= 0) d.ins[d.nIns - 1].c = e.func == GX_F_NOT_LIKE ? 1 : 0;
         *scaleOut = 0;
         break;
       }
@@ -748,6 +824,9 @@ struct VmBuild {
   int nextReg = 0;
   std::map<int, std::pair<int, int>> cache;
   int32_t* wideFlag;
+  // VM_LIKE pattern table of the target desc (null: no value-context LIKE)
+  gxp::LikePat* likePats = nullptr;
+  int32_t* nLikePats = nullptr;
 };
 
 static int vmFetchSlot(VmBuild& B, int kind, int col) {
@@ -853,6 +932,25 @@ static int vmCompile(gx_exec* ex, VmBuild& B, int exprId, int* scaleOut) {
           return -1;
         }
         reg = emit(gxp::VM_STRLEN, allocReg(), col, 0, -1);
+        *scaleOut = 0;
+        break;
+      }
+      if (e.func == GX_F_LIKE || e.func == GX_F_NOT_LIKE) {
+        // LIKE in value context: i64 0/1, NULL when the string is NULL
+        if (!B.likePats) {
+          ex->jaLikeRejected = true;
+          ex->err = "LIKE in value context is not supported in the "
+                    "join-aggregate pipeline";
+          return -1;
+        }
+        gxp::LikePat lp;
+        int col;
+        if (!compileLikeCall(ex, e, *B.colTypes, B.colBase, &col, &lp))
+          return -1;
+        int pi = internLikePat(ex, B.likePats, B.nLikePats, lp);
+        if (pi < 0) return -1;
+        reg = emit(gxp::VM_LIKE, allocReg(), col, pi,
+                   e.func == GX_F_NOT_LIKE ? 1 : 0);
         *scaleOut = 0;
         break;
       }
@@ -990,6 +1088,22 @@ static bool compileTablePred(gx_exec* ex, const PNode& srcNode, int condId,
                              gxp::PredDesc* out, uint8_t* strConst,
                              int32_t* strConstLen) {
   const PExpr& e = ex->plan.exprs[condId];
+  if (e.kind == EK_CALL && (e.func == GX_F_LIKE || e.func == GX_F_NOT_LIKE)) {
+    // general LIKE: the compiled pattern travels inside the PredDesc
+    gxp::LikePat lp;
+    int col;
+    if (!compileLikeCall(ex, e, srcNode.colTypes, 0, &col, &lp)) return false;
+    gxp::PredDesc pd{};
+    pd.kind = gxp::PRED_STR_LIKE;
+    pd.col = col;
+    pd.cmp = e.func == GX_F_LIKE ? GX_F_EQ : GX_F_NE;
+    pd.slot = -1;
+    std::memcpy(pd.strC, lp.chars, sizeof lp.chars);
+    pd.strCLen = lp.n;
+    pd.constU64 = lp.types;
+    *out = pd;
+    return true;
+  }
   if (e.kind == EK_CALL && e.func == GX_F_LIKE_PREFIX && e.args.size() == 2) {
     // LIKE 'abc%' fast path (builtinLikeSig): byte prefix, no PAD trimming
     const PExpr& col = ex->plan.exprs[e.args[0]];
@@ -1481,6 +1595,7 @@ static int32_t compilePostJoinPreds(gx_exec* ex, const PNode& sel,
     const PExpr& e = plan.exprs[cid];
     gxp::JoinPostPred q{};
     bool colcol = e.kind == EK_CALL && e.args.size() == 2 &&
+                  e.func != GX_F_LIKE && e.func != GX_F_NOT_LIKE &&
                   plan.exprs[e.args[0]].kind == EK_COLREF &&
                   plan.exprs[e.args[1]].kind == EK_COLREF;
     if (colcol) {
@@ -1783,6 +1898,8 @@ static int32_t compileProject(gx_exec* ex) {
   B.colFracs = childFracs;
   B.colBase = 0;
   B.wideFlag = &pd.wide;
+  B.likePats = pd.likePats;
+  B.nLikePats = &pd.nLikePats;
   for (int eid : pj.exprs) {
     const PExpr& e = plan.exprs[eid];
     if (e.kind == EK_COLREF) {
@@ -2086,6 +2203,19 @@ static int32_t compileFused(gx_exec* ex) {
       int groupHead = ex->desc.nPreds;
     for (int condId : fusedLeaves) {
       const PExpr& e = plan.exprs[condId];
+      if (e.kind == EK_CALL &&
+          (e.func == GX_F_LIKE || e.func == GX_F_NOT_LIKE)) {
+        // general LIKE in the fused CNF: same PredDesc as every other site
+        if (ex->desc.nPreds >= gxp::kMaxPreds) {
+          ex->err = "too many filter conjuncts";
+          return GX_ERR_INVALID;
+        }
+        gxp::PredDesc pd{};
+        if (!compileTablePred(ex, *src, condId, &pd, nullptr, nullptr))
+          return GX_ERR_INVALID;
+        ex->desc.preds[ex->desc.nPreds++] = pd;
+        continue;
+      }
       if (e.kind == EK_CALL && e.func == GX_F_LIKE_PREFIX &&
           e.args.size() == 2) {
         // LIKE 'abc%' in the fused CNF (byte prefix, no PAD trimming)
@@ -3013,6 +3143,8 @@ static int32_t finalizeFusedBind(gx_exec* ex) {
               ex->vmNextReg <= 12;  // the staged kernel's VmState is 12-reg
     for (int s = 0; s < d.nAccSlots && ok; s++)
       ok = d.accKind[s] == 0;  // staged accumulate is sum-only
+    for (int i = 0; i < d.nIns && ok; i++)
+      ok = d.ins[i].op != gxp::VM_LIKE;  // the staged VM has no string ops
     for (int f = 0; f < d.nFetch && ok; f++)
       ok = d.fetch[f].kind == gxp::FETCH_8B ||
            d.fetch[f].kind == gxp::FETCH_DEC16 ||
@@ -6475,7 +6607,9 @@ gx_exec* gx_build(gx_pb* pb, int32_t root, int32_t device) {
         ex->exprUse.clear();
         ex->vmFreeRegs.clear();
         rc = compileJoinAgg(ex);
-        if (rc != GX_OK) {
+        if (rc != GX_OK && ex->jaLikeRejected) {
+          ex->postSortKeys.clear();
+        } else if (rc != GX_OK) {
           // last resort: general aggregation over materialized joined rows
           // + host post-sort (keys already validated as agg output columns)
           ex->err.clear();

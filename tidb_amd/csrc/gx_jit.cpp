@@ -179,6 +179,20 @@ static void emitRowPipe(std::ostringstream& s, const FusedQueryDesc& d) {
           << ") ? 1 : 0, &ovf); " << nv << " = n" << ins.a << " || n"
           << ins.b << "; }\n";
         break;
+      case gxp::VM_LIKE: {
+        // value-context LIKE: the shared matcher over the desc's pattern
+        // table (loads at use; NULL string -> NULL)
+        const gxp::DevCol& c = d.table.cols[ins.a];
+        s << "  { bool t3 = "
+          << (c.hasNulls ? "colIsNull(d.table.cols[" + std::to_string(ins.a) +
+                               "], row)"
+                         : std::string("false"))
+          << ";\n    " << v << " = VT<WIDE>::fromI64(!t3 && likeColMatch("
+          << "d.table.cols[" << ins.a << "], d.likePats[" << ins.b
+          << "], row) != " << (ins.c != 0 ? "true" : "false")
+          << " ? 1 : 0, &ovf); " << nv << " = t3; }\n";
+        break;
+      }
       case gxp::VM_IF:
         s << "  { bool t = !n" << ins.a << " && VT<WIDE>::cmp(v" << ins.a
           << ", VT<WIDE>::zero()) != 0; " << v << " = t ? v" << ins.b
@@ -838,6 +852,10 @@ __device__ __forceinline__ bool jaRow(const JoinAggDesc& d, int64_t row,
                    "].data)[row]"))
         << ";\n    if (!(pv " << cmpOp(pd.cmp) << " (int64_t)"
         << (int64_t)pd.constU64 << "LL)) return true; }\n";
+    } else if (pd.kind == gxp::PRED_STR_LIKE) {
+      // general LIKE: shared matcher, pattern inside the PredDesc
+      s << "  if (!evalSimplePred(d.probe, d.predP, d.strConst, "
+           "d.strConstLen, row)) return true;\n";
     }
   }
   // key + bloom + slot probe
@@ -959,6 +977,11 @@ static void emitPredInline(std::ostringstream& s, const JoinAggDesc& d,
         << rowVar << "]";
     s << ";\n      if (!(pv " << cmpOp(pd.cmp) << " (int64_t)"
       << (int64_t)pd.constU64 << "LL)) continue; }\n";
+  } else if (pd.kind == gxp::PRED_STR_LIKE) {
+    // general LIKE: shared matcher, pattern inside the PredDesc
+    const char* pdName = &pd == &d.pred0 ? "d.pred0" : "d.pred1";
+    s << "    if (!evalSimplePred(" << tbl << ", " << pdName
+      << ", d.strConst, d.strConstLen, " << rowVar << ")) continue;\n";
   } else {  // PRED_STR_EQ_CONST: literal bytes
     s << "    { int64_t st, en;\n";
     if (c.denseOffsets)

@@ -237,6 +237,18 @@ __device__ __attribute__((always_inline)) inline bool processRow(const FusedQuer
         vm.setNull(ins.dst, nul);
         break;
       }
+      case VM_LIKE: {
+        // LIKE / NOT LIKE in value context: i64 0/1, NULL string -> NULL
+        // (offsets and bytes load at use, not through the fetch pipeline)
+        const DevCol& c = d.table.cols[ins.a];
+        bool nul = colIsNull(c, row);
+        int64_t r = 0;
+        if (!nul)
+          r = likeColMatch(c, d.likePats[ins.b], row) != (ins.c != 0) ? 1 : 0;
+        vm.set(ins.dst, VT<WIDE>::fromI64(r, &ovf));
+        vm.setNull(ins.dst, nul);
+        break;
+      }
       case VM_LOAD_CONST: {
         if (WIDE) {
           Int128 cv = {(uint64_t)d.constLo[ins.a], d.constHi[ins.a]};
@@ -3130,6 +3142,17 @@ __global__ void projectKernel(const ProjDesc* __restrict__ dp) {
                                        gptr<int64_t>(c.offsets)[row];
           vm.set(ins.dst,
                  nul ? VT<WIDE>::zero() : VT<WIDE>::fromI64(len, &ovf));
+          vm.setNull(ins.dst, nul);
+          break;
+        }
+        case VM_LIKE: {
+          // LIKE / NOT LIKE in value context: i64 0/1, NULL string -> NULL
+          const DevCol& c = d.table.cols[ins.a];
+          bool nul = colIsNull(c, row);
+          int64_t r = 0;
+          if (!nul)
+            r = likeColMatch(c, d.likePats[ins.b], row) != (ins.c != 0) ? 1 : 0;
+          vm.set(ins.dst, VT<WIDE>::fromI64(r, &ovf));
           vm.setNull(ins.dst, nul);
           break;
         }

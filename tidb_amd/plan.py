@@ -23,6 +23,25 @@ ORDERS_TYPES = [GX_TYPE_I64, GX_TYPE_I64, GX_TYPE_TIME, GX_TYPE_I64]
 CUSTOMER_TYPES = [GX_TYPE_I64, GX_TYPE_STRING]
 
 
+# general LIKE / NOT LIKE (include/gx_executor.h): args (string column,
+# const pattern [, const i64 escape byte])
+GX_F_LIKE, GX_F_NOT_LIKE = 54, 55
+
+
+def declare_like_helpers(lib):
+    """ctypes signatures of the host-side LIKE helpers (gx_like_compile /
+    gx_like_match); returns lib."""
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    lib.gx_like_compile.restype = ctypes.c_int32
+    lib.gx_like_compile.argtypes = [ctypes.c_char_p, ctypes.c_int32,
+                                    ctypes.c_int32, u8p, u8p, ctypes.c_int32]
+    lib.gx_like_match.restype = ctypes.c_int32
+    lib.gx_like_match.argtypes = [ctypes.c_char_p, ctypes.c_int32,
+                                  ctypes.c_int32, ctypes.c_char_p,
+                                  ctypes.c_int32]
+    return lib
+
+
 def _arr(vals):
     return (ctypes.c_int32 * len(vals))(*vals)
 
