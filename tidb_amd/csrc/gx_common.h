@@ -81,6 +81,19 @@ enum VmOp : int32_t {
                          // string is NULL (offsets load at use)
 };
 
+// Opcode sets of the VM sites, one bit per opcode (1u << VM_x). The probe and
+// glds-staged kernels run the core set, the fused and projection kernels the
+// full one. Device code compiles a kernel's step for its set (gx_vm.h) and
+// the host screens a plan against the set before it picks that site.
+constexpr uint32_t kVmOpsCore =
+    1u << VM_LOAD_DEC | 1u << VM_LOAD_I64 | 1u << VM_LOAD_CONST |
+    1u << VM_ADD | 1u << VM_SUB | 1u << VM_MUL | 1u << VM_SCALE_UP |
+    1u << VM_IFNULL | 1u << VM_ABS | 1u << VM_TIME_EXTRACT | 1u << VM_MAX2 |
+    1u << VM_MIN2 | 1u << VM_CMP | 1u << VM_IF;
+constexpr uint32_t kVmOpsFull = kVmOpsCore | 1u << VM_DIV |
+                                1u << VM_ROUND_SCALE | 1u << VM_STRLEN |
+                                1u << VM_LIKE;
+
 struct VmIns {
   int32_t op;
   int32_t dst;  // register index
@@ -88,6 +101,14 @@ struct VmIns {
   int32_t b;    // register / power
   int32_t c;    // LOAD ops: raw fetch slot (see FetchDesc)
 };
+
+// true when every instruction's opcode is in `ops`
+inline bool vmOpsWithin(const VmIns* ins, int nIns, uint32_t ops) {
+  for (int i = 0; i < nIns; i++)
+    if (ins[i].op < 0 || ins[i].op > 31 || !((ops >> ins[i].op) & 1))
+      return false;
+  return true;
+}
 
 constexpr int kMaxVmIns = 48;
 constexpr int kMaxVmRegs = 14;

@@ -2,7 +2,8 @@
 // kernels. Included by gx_kernels.hip AND by the hipRTC-generated
 // specialized kernels (gx_jit.cpp), so both paths compute identically:
 // Int128 arithmetic, the MyDecimal raw parser, the raw-fetch machinery,
-// group keys, and the LDS/global accumulate helpers.
+// group keys, the LDS/global accumulate helpers and, through gx_vm.h at the
+// end, the expression VM's opcodes.
 #pragma once
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
@@ -908,3 +909,5 @@ __device__ inline unsigned __int128 u128DivBig(unsigned __int128 n,
 }
 
 }  // namespace gxp
+
+#include "gx_vm.h"  // the VM opcodes, built on the helpers above

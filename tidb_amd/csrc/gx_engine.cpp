@@ -3138,13 +3138,13 @@ static int32_t finalizeFusedBind(gx_exec* ex) {
     // The glds-staged kernel is parity-green but measured slower than the
     // plain grouped-fetch kernel on Q1/SF10 (5.48 vs 4.71 ms), so it ships
     // opt-in until the pipelining wins back the staging overhead.
-    bool ok = tab.nRows >= 256 && getenv("GX_GLDS") && !ex->vmHasDiv &&
+    bool ok = tab.nRows >= 256 && getenv("GX_GLDS") &&
               !d.gkey.wideMode &&   // wide keys use the plain kernel
               ex->vmNextReg <= 12;  // the staged kernel's VmState is 12-reg
     for (int s = 0; s < d.nAccSlots && ok; s++)
       ok = d.accKind[s] == 0;  // staged accumulate is sum-only
-    for (int i = 0; i < d.nIns && ok; i++)
-      ok = d.ins[i].op != gxp::VM_LIKE;  // the staged VM has no string ops
+    // the staged VM runs the core opcode set: no division, rounding or strings
+    ok = ok && gxp::vmOpsWithin(d.ins, d.nIns, gxp::kVmOpsCore);
     for (int f = 0; f < d.nFetch && ok; f++)
       ok = d.fetch[f].kind == gxp::FETCH_8B ||
            d.fetch[f].kind == gxp::FETCH_DEC16 ||

@@ -65,17 +65,122 @@ static const char* cmpOp(int cmp) {
   }
 }
 
+// declare every physical VM register once; instructions assign
+static void emitVmRegs(std::ostringstream& s, int nRegs) {
+  for (int r = 0; r < nRegs; r++)
+    s << "  T v" << r << " = VT<WIDE>::zero(); bool n" << r
+      << " = false; (void)v" << r << "; (void)n" << r << ";\n";
+}
+
+// tail of a raw decimal load into register v: a row stored at a smaller frac
+// than the declared one (`frac`) scales up, a larger one is an error
+static void emitDecRescale(std::ostringstream& s, const std::string& v,
+                           int frac) {
+  s << "    if (sc != " << frac << ") {\n"
+    << "      if (sc < " << frac << ") { bool o2 = false; " << v
+    << " = VT<WIDE>::scale10(" << v << ", " << frac
+    << " - sc, &o2); if (o2) { atomicOr(d.errorFlag, WIDE ? kErrOverflow"
+       " : kErrRetryWide); return false; } }\n"
+    << "      else { atomicOr(d.errorFlag, kErrScale); return false; }\n"
+    << "    }\n  }\n";
+}
+
+// emit one non-load VM instruction: the gx_vm.h value function (or the VT<>
+// primitive) with literal operands. A register may be recycled as its own
+// operand, so value (t2) and NULL flag (t3) are computed before either is
+// assigned. Loads are the callers'.
+static void emitVmOp(std::ostringstream& s, const gxp::VmIns& ins, int64_t p10,
+                     const int64_t* constLo, const int64_t* constHi) {
+  auto reg = [](const char* k, int r) { return k + std::to_string(r); };
+  const std::string a = reg("v", ins.a), b = reg("v", ins.b),
+                    c = reg("v", ins.c);
+  const std::string na = reg("n", ins.a), nb = reg("n", ins.b),
+                    nc = reg("n", ins.c);
+  const std::string nab = na + " || " + nb;
+  auto i64 = [](int64_t v) {  // literal that survives INT64_MIN
+    return "(int64_t)" + std::to_string((uint64_t)v) + "ULL";
+  };
+  std::string nul, stmt;  // t3's initial value; statement(s) that set t2
+  switch (ins.op) {
+    case gxp::VM_LOAD_CONST:
+      nul = "false";
+      stmt = "t2 = vmConst<WIDE>(" + i64(constLo[ins.a]) + ", " +
+             i64(constHi[ins.a]) + ");";
+      break;
+    case gxp::VM_ADD:
+      nul = nab;
+      stmt = "t2 = VT<WIDE>::add(" + a + ", " + b + ", &ovf);";
+      break;
+    case gxp::VM_SUB:
+      nul = nab;
+      stmt = "t2 = VT<WIDE>::sub(" + a + ", " + b + ", &ovf);";
+      break;
+    case gxp::VM_MUL:
+      nul = nab;
+      stmt = "if (!t3) t2 = VT<WIDE>::mul(" + a + ", " + b + ", &ovf);";
+      break;
+    case gxp::VM_SCALE_UP:
+      nul = na;
+      stmt = "t2 = VT<WIDE>::mul(" + a + ", VT<WIDE>::fromI64(" + i64(p10) +
+             ", nullptr), &ovf);";
+      break;
+    case gxp::VM_TIME_EXTRACT:
+      nul = na;
+      stmt = "t2 = vmTimeExtract<WIDE>(" + a + ", " + std::to_string(ins.b) +
+             ", &ovf);";
+      break;
+    case gxp::VM_CMP:
+      nul = nab;
+      stmt = "t2 = VT<WIDE>::fromI64(cmpResult(VT<WIDE>::cmp(" + a + ", " + b +
+             "), " + std::to_string(ins.c) + ") ? 1 : 0, &ovf);";
+      break;
+    case gxp::VM_IF:
+      nul = "false";
+      stmt = "bool t = !" + na + " && VT<WIDE>::cmp(" + a +
+             ", VT<WIDE>::zero()) != 0; t2 = t ? " + b + " : " + c +
+             "; t3 = t ? " + nb + " : " + nc + ";";
+      break;
+    case gxp::VM_MAX2:
+    case gxp::VM_MIN2:
+      nul = nab;
+      stmt = "t2 = vmSelectMinMax<WIDE>(" + a + ", " + b + ", " +
+             (ins.op == gxp::VM_MAX2 ? "true" : "false") + ");";
+      break;
+    case gxp::VM_ABS:
+      nul = na;
+      stmt = "t2 = vmAbs<WIDE>(" + a + ", &ovf);";
+      break;
+    case gxp::VM_IFNULL:
+      nul = na + " && " + nb;
+      stmt = "t2 = " + na + " ? " + b + " : " + a + ";";
+      break;
+    case gxp::VM_ROUND_SCALE:
+      nul = na;
+      stmt = "if (!t3 && !vmRoundScale<WIDE>(" + a + ", " +
+             std::to_string(ins.b - ins.c) + ", " + i64(p10) +
+             ", &t2, &ovf, d.errorFlag)) return false;";
+      break;
+    case gxp::VM_DIV:
+      nul = nab;
+      stmt = "if (!t3 && !vmDiv<WIDE>(" + a + ", " + b + ", " +
+             std::to_string(ins.c) + ", &t2, &t3, d.errorFlag)) return false;";
+      break;
+    default:  // not reached: compile() and compileJa() refuse such a plan
+      return;
+  }
+  s << "  { bool t3 = " << nul << "; T t2 = VT<WIDE>::zero(); " << stmt << " "
+    << reg("v", ins.dst) << " = t2; " << reg("n", ins.dst) << " = t3; }\n";
+}
+
 // emit the per-row pipeline with every plan constant baked in
 static void emitRowPipe(std::ostringstream& s, const FusedQueryDesc& d) {
   s << "template <bool WIDE>\n"
        "__device__ __forceinline__ bool rowPipe(const FusedQueryDesc& d, "
        "int64_t row, const RawT& raw, Lds3GroupSlot* lds, uint64_t* mySel) {\n"
-       "  using T = typename VT<WIDE>::T;\n";
-  // registers are RECYCLED by the plan compiler: declare every physical
-  // register once, instructions assign
-  for (int r = 0; r < d.nVmRegs; r++)
-    s << "  T v" << r << " = VT<WIDE>::zero(); bool n" << r
-      << " = false; (void)v" << r << "; (void)n" << r << ";\n";
+       "  using T = typename VT<WIDE>::T;\n"
+       "  bool ovf = false; (void)ovf;\n";
+  // registers are RECYCLED by the plan compiler
+  emitVmRegs(s, d.nVmRegs);
   // ---- predicates (literal) ----
   for (int p = 0; p < d.nPreds; p++) {
     const gxp::PredDesc& pd = d.preds[p];
@@ -135,14 +240,8 @@ static void emitRowPipe(std::ostringstream& s, const FusedQueryDesc& d) {
         s << "  if (!" << nv << ") { int sc;\n"
           << "    if (!parseDecimalRaw<WIDE>(raw.get(" << ins.c << "), &" << v
           << ", &sc, d.errorFlag, " << ins.b << ", " << d.insP10[i] << "LL, "
-          << d.insMagic[i] << "ULL)) return false;\n"
-          << "    if (sc != " << ins.b << ") {\n"
-          << "      if (sc < " << ins.b << ") { bool o2 = false; " << v
-          << " = VT<WIDE>::scale10(" << v << ", " << ins.b
-          << " - sc, &o2); if (o2) { atomicOr(d.errorFlag, WIDE ? kErrOverflow"
-             " : kErrRetryWide); return false; } }\n"
-          << "      else { atomicOr(d.errorFlag, kErrScale); return false; }\n"
-          << "    }\n  }\n";
+          << d.insMagic[i] << "ULL)) return false;\n";
+        emitDecRescale(s, v, ins.b);
         break;
       }
       case gxp::VM_LOAD_I64: {
@@ -156,29 +255,6 @@ static void emitRowPipe(std::ostringstream& s, const FusedQueryDesc& d) {
           << ins.c << ").x, &ovf);\n";
         break;
       }
-      case gxp::VM_LOAD_CONST:
-        s << "  { Int128 cv = {" << (uint64_t)d.constLo[ins.a] << "ULL, (int64_t)"
-          << d.constHi[ins.a] << "LL };\n"
-          << "    if (WIDE) " << v << " = *(T*)&cv;\n"
-          << "    else { int64_t c64 = " << d.constLo[ins.a] << "LL; " << v
-          << " = *(T*)&c64; } }\n"
-          << "  " << nv << " = false;\n";
-        break;
-      case gxp::VM_TIME_EXTRACT: {
-        static const int kSh[6] = {50, 46, 41, 36, 30, 24};
-        static const uint64_t kMk[6] = {0x3FFF, 0xF, 0x1F, 0x1F, 0x3F, 0x3F};
-        s << "  { uint64_t bits = VT<WIDE>::toAcc(v" << ins.a << ").lo; "
-          << v << " = VT<WIDE>::fromI64((int64_t)((bits >> " << kSh[ins.b]
-          << ") & " << kMk[ins.b] << "ULL), &ovf); " << nv << " = n" << ins.a
-          << "; }\n";
-        break;
-      }
-      case gxp::VM_CMP:
-        s << "  { int c = VT<WIDE>::cmp(v" << ins.a << ", v" << ins.b
-          << "); " << v << " = VT<WIDE>::fromI64(cmpResult(c, " << ins.c
-          << ") ? 1 : 0, &ovf); " << nv << " = n" << ins.a << " || n"
-          << ins.b << "; }\n";
-        break;
       case gxp::VM_LIKE: {
         // value-context LIKE: the shared matcher over the desc's pattern
         // table (loads at use; NULL string -> NULL)
@@ -193,110 +269,8 @@ static void emitRowPipe(std::ostringstream& s, const FusedQueryDesc& d) {
           << " ? 1 : 0, &ovf); " << nv << " = t3; }\n";
         break;
       }
-      case gxp::VM_IF:
-        s << "  { bool t = !n" << ins.a << " && VT<WIDE>::cmp(v" << ins.a
-          << ", VT<WIDE>::zero()) != 0; " << v << " = t ? v" << ins.b
-          << " : v" << ins.c << "; " << nv << " = t ? n" << ins.b << " : n"
-          << ins.c << "; }\n";
-        break;
-      case gxp::VM_MAX2:
-      case gxp::VM_MIN2:
-        s << "  { int c = VT<WIDE>::cmp(v" << ins.a << ", v" << ins.b
-          << "); " << v << " = " << (ins.op == gxp::VM_MAX2 ? "c >= 0"
-                                                            : "c <= 0")
-          << " ? v" << ins.a << " : v" << ins.b << "; " << nv << " = n"
-          << ins.a << " || n" << ins.b << "; }\n";
-        break;
-      case gxp::VM_ABS:
-        s << "  { T t2 = v" << ins.a << "; if (VT<WIDE>::cmp(t2, "
-             "VT<WIDE>::zero()) < 0) t2 = VT<WIDE>::sub(VT<WIDE>::zero(), "
-             "t2, &ovf); " << v << " = t2; " << nv << " = n" << ins.a
-          << "; }\n";
-        break;
-      case gxp::VM_IFNULL:
-        s << "  { bool t3 = n" << ins.a << "; " << v << " = t3 ? v" << ins.b
-          << " : v" << ins.a << "; " << nv << " = t3 && n" << ins.b
-          << "; }\n";
-        break;
-      case gxp::VM_ADD:
-        s << "  { T t2 = VT<WIDE>::add(v" << ins.a << ", v" << ins.b
-          << ", &ovf); bool t3 = n" << ins.a << " || n" << ins.b << "; " << v
-          << " = t2; " << nv << " = t3; }\n";
-        break;
-      case gxp::VM_SUB:
-        s << "  { T t2 = VT<WIDE>::sub(v" << ins.a << ", v" << ins.b
-          << ", &ovf); bool t3 = n" << ins.a << " || n" << ins.b << "; " << v
-          << " = t2; " << nv << " = t3; }\n";
-        break;
-      case gxp::VM_MUL:
-        s << "  { bool t3 = n" << ins.a << " || n" << ins.b << ";\n"
-          << "    T t2 = VT<WIDE>::zero();\n"
-          << "    if (!t3) t2 = VT<WIDE>::mul(v" << ins.a << ", v" << ins.b
-          << ", &ovf);\n    " << v << " = t2; " << nv << " = t3; }\n";
-        break;
-      case gxp::VM_SCALE_UP:
-        s << "  { T t2 = VT<WIDE>::mul(v" << ins.a
-          << ", VT<WIDE>::fromI64(" << d.insP10[i] << "LL, nullptr), &ovf); "
-          << "bool t3 = n" << ins.a << "; " << v << " = t2; " << nv
-          << " = t3; }\n";
-        break;
-      case gxp::VM_ROUND_SCALE: {
-        int up = ins.b - ins.c;
-        s << "  { bool t3 = n" << ins.a << ";\n"
-          << "  T t2 = VT<WIDE>::zero();\n"
-          << "  if (!t3) {\n";
-        if (up >= 0) {
-          s << "    t2 = VT<WIDE>::mul(v" << ins.a
-            << ", VT<WIDE>::fromI64(" << d.insP10[i]
-            << "LL, nullptr), &ovf);\n";
-        } else {
-          s << "    Int128 ai = VT<WIDE>::toAcc(v" << ins.a << ");\n"
-            << "    __int128 av = ((__int128)ai.hi << 64) | (__int128)ai.lo;\n"
-            << "    uint64_t dv = " << (uint64_t)d.insP10[i] << "ULL;\n"
-            << "    unsigned __int128 aAbs = (unsigned __int128)(av < 0 ? -av : av);\n"
-            << "    unsigned __int128 q = u128DivU64(aAbs, dv);\n"
-            << "    unsigned __int128 r = aAbs - q * dv;\n"
-            << "    if (2 * (uint64_t)r >= dv) q += 1;\n"
-            << "    __int128 sq = av < 0 ? -(__int128)q : (__int128)q;\n"
-            << "    if (!WIDE && (sq > (__int128)INT64_MAX || sq < (__int128)INT64_MIN)) {\n"
-            << "      atomicOr(d.errorFlag, kErrRetryWide); return false; }\n"
-            << "    if (WIDE) { Int128 rr = {(uint64_t)sq, (int64_t)(sq >> 64)}; "
-               "t2 = *(T*)&rr; }\n"
-            << "    else { int64_t qq = (int64_t)sq; t2 = *(T*)&qq; }\n";
-        }
-        s << "  }\n  " << v << " = t2; " << nv << " = t3; }\n";
-        break;
-      }
-      case gxp::VM_DIV:
-        s << "  { bool t3 = n" << ins.a << " || n" << ins.b << ";\n"
-          << "  T t2 = VT<WIDE>::zero();\n"
-          << "  if (!t3) {\n"
-          << "    Int128 bi = VT<WIDE>::toAcc(v" << ins.b << ");\n"
-          << "    __int128 bv = ((__int128)bi.hi << 64) | (__int128)bi.lo;\n"
-          << "    if (bv == 0) t3 = true;\n"
-          << "    else {\n"
-          << "      Int128 ai = VT<WIDE>::toAcc(v" << ins.a << ");\n"
-          << "      __int128 av = ((__int128)ai.hi << 64) | (__int128)ai.lo;\n"
-          << "      unsigned __int128 p10 = (unsigned __int128)(uint64_t)kP10("
-          << (ins.c > 18 ? 18 : ins.c) << ");\n"
-          << (ins.c > 18 ? std::string("      p10 *= (uint64_t)kP10(") +
-                               std::to_string(ins.c - 18) + ");\n"
-                         : std::string())
-          << "      unsigned __int128 aAbs = (unsigned __int128)(av < 0 ? -av : av);\n"
-          << "      unsigned __int128 lim = ((unsigned __int128)kDivArgMax["
-          << ins.c << "][1] << 64) | kDivArgMax[" << ins.c << "][0];\n"
-          << "      if (aAbs > lim) { atomicOr(d.errorFlag, kErrOverflow); return false; }\n"
-          << "      unsigned __int128 bAbs = (unsigned __int128)(bv < 0 ? -bv : bv);\n"
-          << "      unsigned __int128 num = aAbs * p10;\n"
-          << "      unsigned __int128 uq = (bAbs >> 64) != 0 ? u128DivBig(num, bAbs)\n"
-          << "                                               : u128DivU64(num, (uint64_t)bAbs);\n"
-          << "      __int128 q = ((av < 0) != (bv < 0)) ? -(__int128)uq : (__int128)uq;\n"
-          << "      if (!WIDE && (q > (__int128)INT64_MAX || q < (__int128)INT64_MIN)) {\n"
-          << "        atomicOr(d.errorFlag, kErrRetryWide); return false; }\n"
-          << "      if (WIDE) { Int128 r = {(uint64_t)q, (int64_t)(q >> 64)}; "
-             "t2 = *(T*)&r; }\n"
-          << "      else { int64_t qq = (int64_t)q; t2 = *(T*)&qq; }\n"
-          << "    }\n  }\n  " << v << " = t2; " << nv << " = t3; }\n";
+      default:
+        emitVmOp(s, ins, d.insP10[i], d.constLo, d.constHi);
         break;
     }
   }
@@ -468,21 +442,9 @@ std::string generateSource(const FusedQueryDesc& d) {
 
   std::ostringstream s;
   s << "#include \"gx_common.h\"\n#include \"gx_device.h\"\n"
-       "using namespace gxp;\nusing RawT = " << rawT << ";\n"
-       "#ifndef INT64_MAX\n#define INT64_MAX 0x7fffffffffffffffLL\n"
-       "#define INT64_MIN (-0x7fffffffffffffffLL - 1)\n#endif\n\n";
+       "using namespace gxp;\nusing RawT = " << rawT << ";\n\n";
   emitFetch(s, d);
-  std::string pipe;
-  {
-    std::ostringstream ps;
-    emitRowPipe(ps, d);
-    pipe = ps.str();
-    // inject `bool ovf = false;` after the opening of rowPipe
-    const std::string marker = "  using T = typename VT<WIDE>::T;\n";
-    size_t pos = pipe.find(marker);
-    pipe.insert(pos + marker.size(), "  bool ovf = false; (void)ovf;\n");
-  }
-  s << pipe;
+  emitRowPipe(s, d);
   // kernel wrapper: same prologue/pipeline/epilogue as fusedAggKernel
   s << R"(
 template <bool WIDE>
@@ -575,25 +537,20 @@ extern "C" __global__ void __launch_bounds__(256) genq_wide(const FusedQueryDesc
   return s.str();
 }
 
-// compile (cached by source text); returns nullptr on any failure
-static const JitProg* compileSource(const std::string& src, const char* fn1,
-                                    const char* fn2, std::string* whyNot) {
-  std::lock_guard<std::mutex> lk(cacheMu);
-  auto it = cache().find(src);
-  if (it != cache().end()) return it->second.ok ? &it->second : nullptr;
-  JitProg prog;
+// hipRTC-compile `src` for gfx950 and load the code object; nullptr (and
+// whyNot) on any failure
+static hipModule_t compileModule(const std::string& src, const char* name,
+                                 std::string* whyNot) {
   hiprtcProgram rp;
-  if (hiprtcCreateProgram(&rp, src.c_str(), "genq.cu", 0, nullptr, nullptr) !=
+  if (hiprtcCreateProgram(&rp, src.c_str(), name, 0, nullptr, nullptr) !=
       HIPRTC_SUCCESS) {
     if (whyNot) *whyNot = "hiprtcCreateProgram failed";
-    cache()[src] = prog;
     return nullptr;
   }
   std::string inc = "-I" + headerDir();
   const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17",
                         inc.c_str()};
-  hiprtcResult rc = hiprtcCompileProgram(rp, 4, opts);
-  if (rc != HIPRTC_SUCCESS) {
+  if (hiprtcCompileProgram(rp, 4, opts) != HIPRTC_SUCCESS) {
     if (whyNot) {
       size_t lsz = 0;
       hiprtcGetProgramLogSize(rp, &lsz);
@@ -602,7 +559,6 @@ static const JitProg* compileSource(const std::string& src, const char* fn1,
       *whyNot = "hiprtc compile failed: " + log;
     }
     hiprtcDestroyProgram(&rp);
-    cache()[src] = prog;
     return nullptr;
   }
   size_t csz = 0;
@@ -610,16 +566,30 @@ static const JitProg* compileSource(const std::string& src, const char* fn1,
   std::string code(csz, '\0');
   hiprtcGetCode(rp, &code[0]);
   hiprtcDestroyProgram(&rp);
-  if (hipModuleLoadData(&prog.mod, code.data()) != hipSuccess ||
-      hipModuleGetFunction(&prog.fnNarrow, prog.mod, fn1) != hipSuccess ||
-      hipModuleGetFunction(&prog.fnWide, prog.mod, fn2) != hipSuccess) {
+  hipModule_t mod = nullptr;
+  if (hipModuleLoadData(&mod, code.data()) != hipSuccess) {
     if (whyNot) *whyNot = "hipModule load failed";
-    cache()[src] = prog;
     return nullptr;
   }
-  prog.ok = true;
+  return mod;
+}
+
+// compile (cached by source text); returns nullptr on any failure
+static const JitProg* compileSource(const std::string& src, const char* fn1,
+                                    const char* fn2, std::string* whyNot) {
+  std::lock_guard<std::mutex> lk(cacheMu);
+  auto it = cache().find(src);
+  if (it != cache().end()) return it->second.ok ? &it->second : nullptr;
+  JitProg prog;
+  prog.mod = compileModule(src, "genq.cu", whyNot);
+  if (prog.mod &&
+      hipModuleGetFunction(&prog.fnNarrow, prog.mod, fn1) == hipSuccess &&
+      hipModuleGetFunction(&prog.fnWide, prog.mod, fn2) == hipSuccess)
+    prog.ok = true;
+  else if (prog.mod && whyNot)
+    *whyNot = "hipModule load failed";
   auto& slot = cache()[src] = prog;
-  return &slot;
+  return prog.ok ? &slot : nullptr;
 }
 
 const JitProg* compile(const FusedQueryDesc& d, std::string* whyNot) {
@@ -633,6 +603,11 @@ const JitProg* compile(const FusedQueryDesc& d, std::string* whyNot) {
       if (whyNot) *whyNot = "string builtin not specialized";
       return nullptr;
     }
+  if (!gxp::vmOpsWithin(d.ins, d.nIns, gxp::kVmOpsFull)) {
+    // the interpreted kernel raises the flag for such a plan
+    if (whyNot) *whyNot = "unknown VM opcode not specialized";
+    return nullptr;
+  }
   for (int p = 0; p < d.nPreds; p++)
     if (d.preds[p].orWith > 0) {
       if (whyNot) *whyNot = "disjunctive filter not specialized";
@@ -659,6 +634,11 @@ int launch(const JitProg* prog, bool wide, const FusedQueryDesc* devDesc,
 using gxp::JoinAggDesc;
 
 static void emitJaVm(std::ostringstream& s, const JoinAggDesc& d) {
+  // registers are never recycled here: max dst + 1 covers every one
+  int nRegs = 0;
+  for (int i = 0; i < d.nIns; i++)
+    if (d.ins[i].dst >= nRegs) nRegs = d.ins[i].dst + 1;
+  emitVmRegs(s, nRegs);
   for (int i = 0; i < d.nIns; i++) {
     const gxp::VmIns& ins = d.ins[i];
     std::string v = "v" + std::to_string(ins.dst);
@@ -666,124 +646,48 @@ static void emitJaVm(std::ostringstream& s, const JoinAggDesc& d) {
     switch (ins.op) {
       case gxp::VM_LOAD_DEC: {
         const gxp::DevCol& c = d.probe.cols[ins.a];
-        s << "    T " << v << " = VT<WIDE>::zero(); bool " << nv
-          << " = false;\n";
+        s << "  " << v << " = VT<WIDE>::zero(); " << nv << " = false;\n";
         if (c.hasNulls)
-          s << "    " << nv << " = colIsNull(d.probe.cols[" << ins.a
+          s << "  " << nv << " = colIsNull(d.probe.cols[" << ins.a
             << "], row);\n";
         if (c.units) {
           // proven column: int64 units at the declared frac (= ins.b)
-          s << "    if (!" << nv << ") " << v
+          s << "  if (!" << nv << ") " << v
             << " = VT<WIDE>::fromI64(gptr<int64_t>(d.probe.cols[" << ins.a
             << "].units)[row], nullptr);\n";
           break;
         }
-        s << "    if (!" << nv << ") { int sc;\n";
+        s << "  if (!" << nv << ") { int sc;\n";
         if (ins.c >= 0)
-          s << "      if (!parseDecimalRaw<WIDE>(raw.get(" << ins.c << "), &"
+          s << "    if (!parseDecimalRaw<WIDE>(raw.get(" << ins.c << "), &"
             << v << ", &sc, d.errorFlag, " << ins.b << ", " << d.insP10[i]
             << "LL, " << d.insMagic[i] << "ULL)) return false;\n";
         else
-          s << "      if (!loadDecimalUnits<WIDE>((const uint8_t*)d.probe.cols["
+          s << "    if (!loadDecimalUnits<WIDE>((const uint8_t*)d.probe.cols["
             << ins.a << "].data + row * 40, &" << v << ", &sc, d.errorFlag, "
             << ins.b << ", " << d.insP10[i] << "LL, " << d.insMagic[i]
             << "ULL)) return false;\n";
-        s << "      if (sc != " << ins.b << ") {\n"
-          << "        if (sc < " << ins.b << ") { bool o2 = false; " << v
-          << " = VT<WIDE>::scale10(" << v << ", " << ins.b
-          << " - sc, &o2); if (o2) { atomicOr(d.errorFlag, WIDE ? kErrOverflow"
-             " : kErrRetryWide); return false; } }\n"
-          << "        else { atomicOr(d.errorFlag, kErrScale); return false; }"
-             "\n      }\n    }\n";
+        emitDecRescale(s, v, ins.b);
         break;
       }
       case gxp::VM_LOAD_I64: {
         const gxp::DevCol& c = d.probe.cols[ins.a];
-        s << "    bool " << nv << " = false;\n";
+        s << "  " << nv << " = false;\n";
         if (c.hasNulls)
-          s << "    " << nv << " = colIsNull(d.probe.cols[" << ins.a
+          s << "  " << nv << " = colIsNull(d.probe.cols[" << ins.a
             << "], row);\n";
         if (ins.c >= 0)
-          s << "    T " << v << " = " << nv
+          s << "  " << v << " = " << nv
             << " ? VT<WIDE>::zero() : VT<WIDE>::fromI64((int64_t)raw.get("
             << ins.c << ").x, &ovf);\n";
         else
-          s << "    T " << v << " = " << nv
+          s << "  " << v << " = " << nv
             << " ? VT<WIDE>::zero() : VT<WIDE>::fromI64(gptr<int64_t>(d.probe."
                "cols[" << ins.a << "].data)[row], &ovf);\n";
         break;
       }
-      case gxp::VM_LOAD_CONST:
-        s << "    T " << v << ";\n"
-          << "    { Int128 cv = {" << (uint64_t)d.constLo[ins.a]
-          << "ULL, (int64_t)" << d.constHi[ins.a] << "LL };\n"
-          << "      if (WIDE) " << v << " = *(T*)&cv;\n"
-          << "      else { int64_t c64 = " << d.constLo[ins.a] << "LL; " << v
-          << " = *(T*)&c64; } }\n"
-          << "    const bool " << nv << " = false;\n";
-        break;
-      case gxp::VM_TIME_EXTRACT: {
-        static const int kSh[6] = {50, 46, 41, 36, 30, 24};
-        static const uint64_t kMk[6] = {0x3FFF, 0xF, 0x1F, 0x1F, 0x3F, 0x3F};
-        s << "    T " << v << " = VT<WIDE>::fromI64((int64_t)((VT<WIDE>::toAcc(v"
-          << ins.a << ").lo >> " << kSh[ins.b] << ") & " << kMk[ins.b]
-          << "ULL), &ovf); bool " << nv << " = n" << ins.a << ";\n";
-        break;
-      }
-      case gxp::VM_CMP:
-        s << "    T " << v << " = VT<WIDE>::fromI64(cmpResult(VT<WIDE>::cmp(v"
-          << ins.a << ", v" << ins.b << "), " << ins.c
-          << ") ? 1 : 0, &ovf); bool " << nv << " = n" << ins.a << " || n"
-          << ins.b << ";\n";
-        break;
-      case gxp::VM_IF:
-        s << "    bool t" << ins.dst << " = !n" << ins.a
-          << " && VT<WIDE>::cmp(v" << ins.a << ", VT<WIDE>::zero()) != 0; T "
-          << v << " = t" << ins.dst << " ? v" << ins.b << " : v" << ins.c
-          << "; bool " << nv << " = t" << ins.dst << " ? n" << ins.b
-          << " : n" << ins.c << ";\n";
-        break;
-      case gxp::VM_MAX2:
-      case gxp::VM_MIN2:
-        s << "    T " << v << " = VT<WIDE>::cmp(v" << ins.a << ", v" << ins.b
-          << ") " << (ins.op == gxp::VM_MAX2 ? ">= 0" : "<= 0") << " ? v"
-          << ins.a << " : v" << ins.b << "; bool " << nv << " = n" << ins.a
-          << " || n" << ins.b << ";\n";
-        break;
-      case gxp::VM_ABS:
-        s << "    T " << v << " = v" << ins.a << "; if (VT<WIDE>::cmp(" << v
-          << ", VT<WIDE>::zero()) < 0) " << v << " = VT<WIDE>::sub("
-             "VT<WIDE>::zero(), " << v << ", &ovf); bool " << nv << " = n"
-          << ins.a << ";\n";
-        break;
-      case gxp::VM_IFNULL:
-        s << "    T " << v << " = n" << ins.a << " ? v" << ins.b << " : v"
-          << ins.a << "; bool " << nv << " = n" << ins.a << " && n" << ins.b
-          << ";\n";
-        break;
-      case gxp::VM_ADD:
-        s << "    T " << v << " = VT<WIDE>::add(v" << ins.a << ", v" << ins.b
-          << ", &ovf); bool " << nv << " = n" << ins.a << " || n" << ins.b
-          << ";\n";
-        break;
-      case gxp::VM_SUB:
-        s << "    T " << v << " = VT<WIDE>::sub(v" << ins.a << ", v" << ins.b
-          << ", &ovf); bool " << nv << " = n" << ins.a << " || n" << ins.b
-          << ";\n";
-        break;
-      case gxp::VM_MUL:
-        s << "    bool " << nv << " = n" << ins.a << " || n" << ins.b << ";\n"
-          << "    T " << v << " = VT<WIDE>::zero();\n"
-          << "    if (!" << nv << ") " << v << " = VT<WIDE>::mul(v" << ins.a
-          << ", v" << ins.b << ", &ovf);\n";
-        break;
-      case gxp::VM_SCALE_UP:
-        s << "    T " << v << " = VT<WIDE>::mul(v" << ins.a
-          << ", VT<WIDE>::fromI64(" << d.insP10[i]
-          << "LL, nullptr), &ovf); bool " << nv << " = n" << ins.a << ";\n";
-        break;
       default:
-        s << "    #error unsupported op\n";
+        emitVmOp(s, ins, d.insP10[i], d.constLo, d.constHi);
         break;
     }
   }
@@ -934,6 +838,11 @@ const JitProg* compileJa(const JoinAggDesc& d, std::string* whyNot) {
   }
   if (d.chained || d.nPredPx > 0) {
     if (whyNot) *whyNot = "chained/multi-conjunct probe not specialized";
+    return nullptr;
+  }
+  if (!gxp::vmOpsWithin(d.ins, d.nIns, gxp::kVmOpsCore)) {
+    // the interpreted probe kernel raises the flag for such a plan
+    if (whyNot) *whyNot = "VM opcode outside the probe set not specialized";
     return nullptr;
   }
   std::string src = generateJaSource(d);
@@ -1208,36 +1117,14 @@ const JaBuildProg* compileJaBuild(const JoinAggDesc& d, std::string* whyNot) {
   auto it = buildCache().find(src);
   if (it != buildCache().end()) return it->second.ok ? &it->second : nullptr;
   JaBuildProg prog;
-  hiprtcProgram rp;
-  if (hiprtcCreateProgram(&rp, src.c_str(), "genjab.cu", 0, nullptr,
-                          nullptr) != HIPRTC_SUCCESS) {
-    if (whyNot) *whyNot = "hiprtcCreateProgram failed";
+  prog.mod = compileModule(src, "genjab.cu", whyNot);
+  if (!prog.mod) {
     buildCache()[src] = prog;
     return nullptr;
   }
-  std::string inc = "-I" + headerDir();
-  const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17",
-                        inc.c_str()};
-  if (hiprtcCompileProgram(rp, 4, opts) != HIPRTC_SUCCESS) {
-    if (whyNot) {
-      size_t lsz = 0;
-      hiprtcGetProgramLogSize(rp, &lsz);
-      std::string log(lsz, '\0');
-      if (lsz) hiprtcGetProgramLog(rp, &log[0]);
-      *whyNot = "hiprtc compile failed: " + log;
-    }
-    hiprtcDestroyProgram(&rp);
-    buildCache()[src] = prog;
-    return nullptr;
-  }
-  size_t csz = 0;
-  hiprtcGetCodeSize(rp, &csz);
-  std::string code(csz, '\0');
-  hiprtcGetCode(rp, &code[0]);
-  hiprtcDestroyProgram(&rp);
   static const char* names[4] = {"genja_count0", "genja_build0",
                                  "genja_count1", "genja_build1"};
-  bool ok = hipModuleLoadData(&prog.mod, code.data()) == hipSuccess;
+  bool ok = true;
   for (int i = 0; ok && i < 4; i++)
     ok = hipModuleGetFunction(&prog.fn[i], prog.mod, names[i]) == hipSuccess;
   if (!ok) {

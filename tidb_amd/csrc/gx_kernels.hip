@@ -133,8 +133,9 @@ __global__ void genLineitemKernel(DevTable tab, int64_t rowBegin, int64_t nRows,
 
 
 // per-row pipeline after the raw fetch: filter -> VM -> LDS aggregate.
-// Returns false on a hard failure (error flag already set).
-template <bool WIDE, bool DIVOK, typename VMT, bool WK = false, typename RAWT>
+// Returns false on a hard failure (error flag already set). OPS is the VM
+// opcode set compiled into this variant (gx_vm.h vmStep).
+template <bool WIDE, uint32_t OPS, typename VMT, bool WK = false, typename RAWT>
 __device__ __attribute__((always_inline)) inline bool processRow(const FusedQueryDesc& d, int64_t row,
                                   const RAWT& raw, Lds3GroupSlot* lds,
                                   uint64_t* mySel,
@@ -249,194 +250,11 @@ __device__ __attribute__((always_inline)) inline bool processRow(const FusedQuer
         vm.setNull(ins.dst, nul);
         break;
       }
-      case VM_LOAD_CONST: {
-        if (WIDE) {
-          Int128 cv = {(uint64_t)d.constLo[ins.a], d.constHi[ins.a]};
-          vm.set(ins.dst, *(typename VT<WIDE>::T*)&cv);
-        } else {
-          // engine guarantees narrow-mode consts fit i64 (else it forces WIDE)
-          int64_t cv = d.constLo[ins.a];
-          vm.set(ins.dst, *(typename VT<WIDE>::T*)&cv);
-        }
-        vm.setNull(ins.dst, false);
-        break;
-      }
-      case VM_ADD:
-        vm.set(ins.dst, VT<WIDE>::add(vm.get(ins.a), vm.get(ins.b), &ovf));
-        vm.setNull(ins.dst, vm.isNull(ins.a) || vm.isNull(ins.b));
-        break;
-      case VM_SUB:
-        vm.set(ins.dst, VT<WIDE>::sub(vm.get(ins.a), vm.get(ins.b), &ovf));
-        vm.setNull(ins.dst, vm.isNull(ins.a) || vm.isNull(ins.b));
-        break;
-      case VM_TIME_EXTRACT: {
-        // CoreTime bitfield (core_time.go): year@50:14 month@46:4 day@41:5
-        // hour@36:5 minute@30:6 second@24:6
-        constexpr int kShift[6] = {50, 46, 41, 36, 30, 24};
-        constexpr uint64_t kMask[6] = {0x3FFF, 0xF, 0x1F, 0x1F, 0x3F, 0x3F};
-        uint64_t bits = VT<WIDE>::toAcc(vm.get(ins.a)).lo;
-        int64_t f = (int64_t)((bits >> kShift[ins.b]) & kMask[ins.b]);
-        vm.set(ins.dst, VT<WIDE>::fromI64(f, &ovf));
-        vm.setNull(ins.dst, vm.isNull(ins.a));
-        break;
-      }
-      case VM_CMP: {
-        // comparisons in VALUE context (builtin_compare_vec family): i64
-        // 0/1, NULL if either operand is NULL
-        int c = VT<WIDE>::cmp(vm.get(ins.a), vm.get(ins.b));
-        vm.set(ins.dst, VT<WIDE>::fromI64(cmpResult(c, ins.c) ? 1 : 0, &ovf));
-        vm.setNull(ins.dst, vm.isNull(ins.a) || vm.isNull(ins.b));
-        break;
-      }
-      case VM_IF: {
-        // builtinIfSig: NULL/0 cond -> else branch; result = chosen branch
-        bool t = !vm.isNull(ins.a) &&
-                 VT<WIDE>::cmp(vm.get(ins.a), VT<WIDE>::zero()) != 0;
-        vm.set(ins.dst, t ? vm.get(ins.b) : vm.get(ins.c));
-        vm.setNull(ins.dst, t ? vm.isNull(ins.b) : vm.isNull(ins.c));
-        break;
-      }
-      case VM_MAX2:
-      case VM_MIN2: {
-        // builtinGreatest/Least*Sig: NULL if either operand is NULL
-        typename VT<WIDE>::T va = vm.get(ins.a), vb = vm.get(ins.b);
-        int c = VT<WIDE>::cmp(va, vb);
-        vm.set(ins.dst, (ins.op == VM_MAX2) == (c >= 0) ? va : vb);
-        vm.setNull(ins.dst, vm.isNull(ins.a) || vm.isNull(ins.b));
-        break;
-      }
-      case VM_ABS: {
-        // builtinAbs*Sig; narrow INT64_MIN -> wide retry via mul overflow
-        typename VT<WIDE>::T av = vm.get(ins.a);
-        if (VT<WIDE>::cmp(av, VT<WIDE>::zero()) < 0)
-          av = VT<WIDE>::sub(VT<WIDE>::zero(), av, &ovf);
-        vm.set(ins.dst, av);
-        vm.setNull(ins.dst, vm.isNull(ins.a));
-        break;
-      }
-      case VM_IFNULL: {
-        // builtinIfNullSig: first non-NULL operand; NULL only if both are
-        bool an = vm.isNull(ins.a);
-        vm.set(ins.dst, an ? vm.get(ins.b) : vm.get(ins.a));
-        vm.setNull(ins.dst, an && vm.isNull(ins.b));
-        break;
-      }
-      case VM_MUL: {
-        bool nul = vm.isNull(ins.a) || vm.isNull(ins.b);
-        typename VT<WIDE>::T v = VT<WIDE>::zero();
-        if (!nul) v = VT<WIDE>::mul(vm.get(ins.a), vm.get(ins.b), &ovf);
-        vm.set(ins.dst, v);
-        vm.setNull(ins.dst, nul);
-        break;
-      }
-      case VM_SCALE_UP:
-        vm.set(ins.dst,
-               VT<WIDE>::mul(vm.get(ins.a),
-                             VT<WIDE>::fromI64(d.insP10[i], nullptr), &ovf));
-        vm.setNull(ins.dst, vm.isNull(ins.a));
-        break;
-      case VM_ROUND_SCALE: {
-        // cast family: round_half_up from scale ins.c to scale ins.b
-        // (ProduceDecWithSpecifiedTp datum.go:1629; ToInt when the engine
-        // lowered cast-as-int to target scale 0)
-        bool nul = vm.isNull(ins.a);
-        typename VT<WIDE>::T v = VT<WIDE>::zero();
-        if (!nul) {
-          int up = ins.b - ins.c;
-          if (up >= 0) {
-            v = VT<WIDE>::mul(vm.get(ins.a),
-                              VT<WIDE>::fromI64(d.insP10[i], nullptr), &ovf);
-          } else {
-            Int128 ai = VT<WIDE>::toAcc(vm.get(ins.a));
-            __int128 av = ((__int128)ai.hi << 64) | (__int128)ai.lo;
-            uint64_t div = (uint64_t)d.insP10[i];  // 10^(c-b), <= 10^18
-            unsigned __int128 aAbs = (unsigned __int128)(av < 0 ? -av : av);
-            unsigned __int128 q = u128DivU64(aAbs, div);
-            unsigned __int128 r = aAbs - q * div;
-            if (2 * (uint64_t)r >= div) q += 1;  // half away from zero
-            __int128 sq = av < 0 ? -(__int128)q : (__int128)q;
-            if (!WIDE &&
-                (sq > (__int128)INT64_MAX || sq < (__int128)INT64_MIN)) {
-              atomicOr(d.errorFlag, kErrRetryWide);
-              bad = true;
-              break;
-            }
-            if (WIDE) {
-              Int128 rr = {(uint64_t)sq, (int64_t)(sq >> 64)};
-              v = *(typename VT<WIDE>::T*)&rr;
-            } else {
-              int64_t qq = (int64_t)sq;
-              v = *(typename VT<WIDE>::T*)&qq;
-            }
-          }
-        }
-        vm.set(ins.dst, v);
-        vm.setNull(ins.dst, nul);
-        break;
-      }
-      case VM_DIV: {
-        if constexpr (!DIVOK) {
-          // engine launches the DIVOK variant for plans containing DIV;
-          // reaching here means a dispatch bug -- fail loudly
-          atomicOr(d.errorFlag, kErrBadDecimal);
+      default:
+        if (!vmStep<WIDE, OPS>(vm, ins, d.insP10[i], d.constLo, d.constHi,
+                               d.errorFlag, &ovf))
           bad = true;
-          break;
-        } else {
-        // DecimalDiv (mydecimal.go:1311, doDiv:1168): quotient truncated
-        // toward zero at the word-granular result scale; ins.c holds the
-        // exponent e with result = trunc(a * 10^e / b). Division by zero
-        // yields NULL (builtin_arithmetic_vec.go:92 handleDivisionByZero).
-        bool nul = vm.isNull(ins.a) || vm.isNull(ins.b);
-        typename VT<WIDE>::T v = VT<WIDE>::zero();
-        if (!nul) {
-          Int128 bi = VT<WIDE>::toAcc(vm.get(ins.b));
-          __int128 bv = ((__int128)bi.hi << 64) | (__int128)bi.lo;
-          if (bv == 0) {
-            nul = true;
-          } else {
-            Int128 ai = VT<WIDE>::toAcc(vm.get(ins.a));
-            __int128 av = ((__int128)ai.hi << 64) | (__int128)ai.lo;
-            int e = ins.c;
-            unsigned __int128 p10 =
-                (unsigned __int128)(uint64_t)kP10(e > 18 ? 18 : e);
-            if (e > 18) p10 *= (uint64_t)kP10(e - 18);
-            unsigned __int128 aAbs =
-                (unsigned __int128)(av < 0 ? -av : av);
-            unsigned __int128 lim =
-                ((unsigned __int128)kDivArgMax[e][1] << 64) | kDivArgMax[e][0];
-            if (aAbs > lim) {
-              atomicOr(d.errorFlag, kErrOverflow);
-              bad = true;
-              break;
-            }
-            unsigned __int128 bAbs =
-                (unsigned __int128)(bv < 0 ? -bv : bv);
-            unsigned __int128 num = aAbs * p10;
-            unsigned __int128 uq = (bAbs >> 64) != 0
-                                       ? u128DivBig(num, bAbs)
-                                       : u128DivU64(num, (uint64_t)bAbs);
-            bool negq = (av < 0) != (bv < 0);
-            __int128 q = negq ? -(__int128)uq : (__int128)uq;
-            if (!WIDE &&
-                (q > (__int128)INT64_MAX || q < (__int128)INT64_MIN)) {
-              atomicOr(d.errorFlag, kErrRetryWide);
-              bad = true;
-              break;
-            }
-            if (WIDE) {
-              Int128 r = {(uint64_t)q, (int64_t)(q >> 64)};
-              v = *(typename VT<WIDE>::T*)&r;
-            } else {
-              int64_t qq = (int64_t)q;
-              v = *(typename VT<WIDE>::T*)&qq;
-            }
-          }
-        }
-        vm.set(ins.dst, v);
-        vm.setNull(ins.dst, nul);
         break;
-        }
-      }
     }
   }
   if (ovf) {
@@ -649,11 +467,14 @@ __global__ void fusedAggKernel(const FusedQueryDesc* __restrict__ dp) {
       if (rB < end) fetchRow(d.table, d.fetch, d.nFetch, rB, rawB);
       using VMT = typename std::conditional<NVM <= 12, VmState<WIDE>,
                                             VmState14<WIDE>>::type;
-      if (!processRow<WIDE, DIVOK, VMT, WK>(d, row, rawA, lds3, &mySel,
+      // engine launches the DIVOK variant for plans containing DIV; in the
+      // others a DIV is a dispatch bug and fails loudly
+      constexpr uint32_t OPS = DIVOK ? kVmOpsFull : kVmOpsFull & ~(1u << VM_DIV);
+      if (!processRow<WIDE, OPS, VMT, WK>(d, row, rawA, lds3, &mySel,
                                             wkCacheH, wkCacheS)) { failed = true; break; }
       const int64_t rA2 = row + 2 * stride;
       if (rA2 < end) fetchRow(d.table, d.fetch, d.nFetch, rA2, rawA);
-      if (rB < end && !processRow<WIDE, DIVOK, VMT, WK>(d, rB, rawB, lds3, &mySel,
+      if (rB < end && !processRow<WIDE, OPS, VMT, WK>(d, rB, rawB, lds3, &mySel,
                                                         wkCacheH, wkCacheS)) failed = true;
     }
   }
@@ -1074,83 +895,10 @@ __global__ void jaProbeKernel(const JoinAggDesc* __restrict__ dp) {
           vm.setNull(ins.dst, nul);
           break;
         }
-        case VM_LOAD_CONST: {
-          if (WIDE) {
-            Int128 cv = {(uint64_t)d.constLo[ins.a], d.constHi[ins.a]};
-            vm.set(ins.dst, *(typename VT<WIDE>::T*)&cv);
-          } else {
-            int64_t cv = d.constLo[ins.a];
-            vm.set(ins.dst, *(typename VT<WIDE>::T*)&cv);
-          }
-          vm.setNull(ins.dst, false);
-          break;
-        }
-        case VM_ADD:
-          vm.set(ins.dst, VT<WIDE>::add(vm.get(ins.a), vm.get(ins.b), &ovf));
-          vm.setNull(ins.dst, vm.isNull(ins.a) || vm.isNull(ins.b));
-          break;
-        case VM_SUB:
-          vm.set(ins.dst, VT<WIDE>::sub(vm.get(ins.a), vm.get(ins.b), &ovf));
-          vm.setNull(ins.dst, vm.isNull(ins.a) || vm.isNull(ins.b));
-          break;
-        case VM_TIME_EXTRACT: {
-          constexpr int kShift[6] = {50, 46, 41, 36, 30, 24};
-          constexpr uint64_t kMask[6] = {0x3FFF, 0xF, 0x1F, 0x1F, 0x3F, 0x3F};
-          uint64_t bits = VT<WIDE>::toAcc(vm.get(ins.a)).lo;
-          int64_t f = (int64_t)((bits >> kShift[ins.b]) & kMask[ins.b]);
-          vm.set(ins.dst, VT<WIDE>::fromI64(f, &ovf));
-          vm.setNull(ins.dst, vm.isNull(ins.a));
-          break;
-        }
-        case VM_CMP: {
-          int c = VT<WIDE>::cmp(vm.get(ins.a), vm.get(ins.b));
-          vm.set(ins.dst,
-                 VT<WIDE>::fromI64(cmpResult(c, ins.c) ? 1 : 0, &ovf));
-          vm.setNull(ins.dst, vm.isNull(ins.a) || vm.isNull(ins.b));
-          break;
-        }
-        case VM_IF: {
-          bool t = !vm.isNull(ins.a) &&
-                   VT<WIDE>::cmp(vm.get(ins.a), VT<WIDE>::zero()) != 0;
-          vm.set(ins.dst, t ? vm.get(ins.b) : vm.get(ins.c));
-          vm.setNull(ins.dst, t ? vm.isNull(ins.b) : vm.isNull(ins.c));
-          break;
-        }
-        case VM_MAX2:
-        case VM_MIN2: {
-          typename VT<WIDE>::T va = vm.get(ins.a), vb = vm.get(ins.b);
-          int c = VT<WIDE>::cmp(va, vb);
-          vm.set(ins.dst, (ins.op == VM_MAX2) == (c >= 0) ? va : vb);
-          vm.setNull(ins.dst, vm.isNull(ins.a) || vm.isNull(ins.b));
-          break;
-        }
-        case VM_ABS: {
-          typename VT<WIDE>::T av = vm.get(ins.a);
-          if (VT<WIDE>::cmp(av, VT<WIDE>::zero()) < 0)
-            av = VT<WIDE>::sub(VT<WIDE>::zero(), av, &ovf);
-          vm.set(ins.dst, av);
-          vm.setNull(ins.dst, vm.isNull(ins.a));
-          break;
-        }
-        case VM_IFNULL: {
-          bool an = vm.isNull(ins.a);
-          vm.set(ins.dst, an ? vm.get(ins.b) : vm.get(ins.a));
-          vm.setNull(ins.dst, an && vm.isNull(ins.b));
-          break;
-        }
-        case VM_MUL: {
-          bool nul = vm.isNull(ins.a) || vm.isNull(ins.b);
-          typename VT<WIDE>::T v = VT<WIDE>::zero();
-          if (!nul) v = VT<WIDE>::mul(vm.get(ins.a), vm.get(ins.b), &ovf);
-          vm.set(ins.dst, v);
-          vm.setNull(ins.dst, nul);
-          break;
-        }
-        case VM_SCALE_UP:
-          vm.set(ins.dst,
-                 VT<WIDE>::mul(vm.get(ins.a),
-                               VT<WIDE>::fromI64(d.insP10[i], nullptr), &ovf));
-          vm.setNull(ins.dst, vm.isNull(ins.a));
+        default:
+          if (!vmStep<WIDE, kVmOpsCore>(vm, ins, d.insP10[i], d.constLo,
+                                        d.constHi, d.errorFlag, &ovf))
+            bad = true;
           break;
       }
     }
@@ -1532,82 +1280,10 @@ __device__ __attribute__((always_inline)) inline bool processRowStaged(
         vm.set(ins.dst, VT<WIDE>::fromI64((int64_t)raw.get(ins.c).x, &ovf));
         vm.setNull(ins.dst, false);
         break;
-      case VM_LOAD_CONST: {
-        if (WIDE) {
-          Int128 cv = {(uint64_t)d.constLo[ins.a], d.constHi[ins.a]};
-          vm.set(ins.dst, *(typename VT<WIDE>::T*)&cv);
-        } else {
-          int64_t cv = d.constLo[ins.a];
-          vm.set(ins.dst, *(typename VT<WIDE>::T*)&cv);
-        }
-        vm.setNull(ins.dst, false);
-        break;
-      }
-      case VM_ADD:
-        vm.set(ins.dst, VT<WIDE>::add(vm.get(ins.a), vm.get(ins.b), &ovf));
-        break;
-      case VM_SUB:
-        vm.set(ins.dst, VT<WIDE>::sub(vm.get(ins.a), vm.get(ins.b), &ovf));
-        break;
-      case VM_TIME_EXTRACT: {
-        // CoreTime bitfield (core_time.go): year@50:14 month@46:4 day@41:5
-        // hour@36:5 minute@30:6 second@24:6
-        constexpr int kShift[6] = {50, 46, 41, 36, 30, 24};
-        constexpr uint64_t kMask[6] = {0x3FFF, 0xF, 0x1F, 0x1F, 0x3F, 0x3F};
-        uint64_t bits = VT<WIDE>::toAcc(vm.get(ins.a)).lo;
-        int64_t f = (int64_t)((bits >> kShift[ins.b]) & kMask[ins.b]);
-        vm.set(ins.dst, VT<WIDE>::fromI64(f, &ovf));
-        vm.setNull(ins.dst, vm.isNull(ins.a));
-        break;
-      }
-      case VM_CMP: {
-        // comparisons in VALUE context (builtin_compare_vec family): i64
-        // 0/1, NULL if either operand is NULL
-        int c = VT<WIDE>::cmp(vm.get(ins.a), vm.get(ins.b));
-        vm.set(ins.dst, VT<WIDE>::fromI64(cmpResult(c, ins.c) ? 1 : 0, &ovf));
-        vm.setNull(ins.dst, vm.isNull(ins.a) || vm.isNull(ins.b));
-        break;
-      }
-      case VM_IF: {
-        // builtinIfSig: NULL/0 cond -> else branch; result = chosen branch
-        bool t = !vm.isNull(ins.a) &&
-                 VT<WIDE>::cmp(vm.get(ins.a), VT<WIDE>::zero()) != 0;
-        vm.set(ins.dst, t ? vm.get(ins.b) : vm.get(ins.c));
-        vm.setNull(ins.dst, t ? vm.isNull(ins.b) : vm.isNull(ins.c));
-        break;
-      }
-      case VM_MAX2:
-      case VM_MIN2: {
-        // builtinGreatest/Least*Sig: NULL if either operand is NULL
-        typename VT<WIDE>::T va = vm.get(ins.a), vb = vm.get(ins.b);
-        int c = VT<WIDE>::cmp(va, vb);
-        vm.set(ins.dst, (ins.op == VM_MAX2) == (c >= 0) ? va : vb);
-        vm.setNull(ins.dst, vm.isNull(ins.a) || vm.isNull(ins.b));
-        break;
-      }
-      case VM_ABS: {
-        // builtinAbs*Sig; narrow INT64_MIN -> wide retry via mul overflow
-        typename VT<WIDE>::T av = vm.get(ins.a);
-        if (VT<WIDE>::cmp(av, VT<WIDE>::zero()) < 0)
-          av = VT<WIDE>::sub(VT<WIDE>::zero(), av, &ovf);
-        vm.set(ins.dst, av);
-        vm.setNull(ins.dst, vm.isNull(ins.a));
-        break;
-      }
-      case VM_IFNULL: {
-        // builtinIfNullSig: first non-NULL operand; NULL only if both are
-        bool an = vm.isNull(ins.a);
-        vm.set(ins.dst, an ? vm.get(ins.b) : vm.get(ins.a));
-        vm.setNull(ins.dst, an && vm.isNull(ins.b));
-        break;
-      }
-      case VM_MUL:
-        vm.set(ins.dst, VT<WIDE>::mul(vm.get(ins.a), vm.get(ins.b), &ovf));
-        break;
-      case VM_SCALE_UP:
-        vm.set(ins.dst,
-               VT<WIDE>::mul(vm.get(ins.a),
-                             VT<WIDE>::fromI64(d.insP10[i0], nullptr), &ovf));
+      default:
+        if (!vmStep<WIDE, kVmOpsCore>(vm, ins, d.insP10[i0], d.constLo,
+                                      d.constHi, d.errorFlag, &ovf))
+          bad = true;
         break;
     }
   }
@@ -3156,176 +2832,10 @@ __global__ void projectKernel(const ProjDesc* __restrict__ dp) {
           vm.setNull(ins.dst, nul);
           break;
         }
-        case VM_LOAD_CONST: {
-          if (WIDE) {
-            Int128 cv = {(uint64_t)d.constLo[ins.a], d.constHi[ins.a]};
-            vm.set(ins.dst, *(typename VT<WIDE>::T*)&cv);
-          } else {
-            int64_t cv = d.constLo[ins.a];
-            vm.set(ins.dst, *(typename VT<WIDE>::T*)&cv);
-          }
-          vm.setNull(ins.dst, false);
-          break;
-        }
-        case VM_ADD:
-          vm.set(ins.dst, VT<WIDE>::add(vm.get(ins.a), vm.get(ins.b), &ovf));
-          vm.setNull(ins.dst, vm.isNull(ins.a) || vm.isNull(ins.b));
-          break;
-        case VM_SUB:
-          vm.set(ins.dst, VT<WIDE>::sub(vm.get(ins.a), vm.get(ins.b), &ovf));
-          vm.setNull(ins.dst, vm.isNull(ins.a) || vm.isNull(ins.b));
-          break;
-        case VM_TIME_EXTRACT: {
-          constexpr int kShift[6] = {50, 46, 41, 36, 30, 24};
-          constexpr uint64_t kMask[6] = {0x3FFF, 0xF, 0x1F, 0x1F, 0x3F, 0x3F};
-          uint64_t bits = VT<WIDE>::toAcc(vm.get(ins.a)).lo;
-          int64_t f = (int64_t)((bits >> kShift[ins.b]) & kMask[ins.b]);
-          vm.set(ins.dst, VT<WIDE>::fromI64(f, &ovf));
-          vm.setNull(ins.dst, vm.isNull(ins.a));
-          break;
-        }
-        case VM_CMP: {
-          int c = VT<WIDE>::cmp(vm.get(ins.a), vm.get(ins.b));
-          vm.set(ins.dst,
-                 VT<WIDE>::fromI64(cmpResult(c, ins.c) ? 1 : 0, &ovf));
-          vm.setNull(ins.dst, vm.isNull(ins.a) || vm.isNull(ins.b));
-          break;
-        }
-        case VM_IF: {
-          bool t = !vm.isNull(ins.a) &&
-                   VT<WIDE>::cmp(vm.get(ins.a), VT<WIDE>::zero()) != 0;
-          vm.set(ins.dst, t ? vm.get(ins.b) : vm.get(ins.c));
-          vm.setNull(ins.dst, t ? vm.isNull(ins.b) : vm.isNull(ins.c));
-          break;
-        }
-        case VM_MAX2:
-        case VM_MIN2: {
-          typename VT<WIDE>::T va = vm.get(ins.a), vb = vm.get(ins.b);
-          int c = VT<WIDE>::cmp(va, vb);
-          vm.set(ins.dst, (ins.op == VM_MAX2) == (c >= 0) ? va : vb);
-          vm.setNull(ins.dst, vm.isNull(ins.a) || vm.isNull(ins.b));
-          break;
-        }
-        case VM_ABS: {
-          typename VT<WIDE>::T av = vm.get(ins.a);
-          if (VT<WIDE>::cmp(av, VT<WIDE>::zero()) < 0)
-            av = VT<WIDE>::sub(VT<WIDE>::zero(), av, &ovf);
-          vm.set(ins.dst, av);
-          vm.setNull(ins.dst, vm.isNull(ins.a));
-          break;
-        }
-        case VM_IFNULL: {
-          bool an = vm.isNull(ins.a);
-          vm.set(ins.dst, an ? vm.get(ins.b) : vm.get(ins.a));
-          vm.setNull(ins.dst, an && vm.isNull(ins.b));
-          break;
-        }
-        case VM_MUL: {
-          bool nul = vm.isNull(ins.a) || vm.isNull(ins.b);
-          typename VT<WIDE>::T v = VT<WIDE>::zero();
-          if (!nul) v = VT<WIDE>::mul(vm.get(ins.a), vm.get(ins.b), &ovf);
-          vm.set(ins.dst, v);
-          vm.setNull(ins.dst, nul);
-          break;
-        }
-        case VM_SCALE_UP:
-          vm.set(ins.dst,
-                 VT<WIDE>::mul(vm.get(ins.a),
-                               VT<WIDE>::fromI64(d.insP10[i], nullptr), &ovf));
-          vm.setNull(ins.dst, vm.isNull(ins.a));
-          break;
-        case VM_ROUND_SCALE: {
-          bool nul = vm.isNull(ins.a);
-          typename VT<WIDE>::T v = VT<WIDE>::zero();
-          if (!nul) {
-            int up = ins.b - ins.c;
-            if (up >= 0) {
-              v = VT<WIDE>::mul(vm.get(ins.a),
-                                VT<WIDE>::fromI64(d.insP10[i], nullptr), &ovf);
-            } else {
-              Int128 ai = VT<WIDE>::toAcc(vm.get(ins.a));
-              __int128 av = ((__int128)ai.hi << 64) | (__int128)ai.lo;
-              uint64_t div = (uint64_t)d.insP10[i];
-              unsigned __int128 aAbs = (unsigned __int128)(av < 0 ? -av : av);
-              unsigned __int128 q = u128DivU64(aAbs, div);
-              unsigned __int128 r = aAbs - q * div;
-              if (2 * (uint64_t)r >= div) q += 1;
-              __int128 sq = av < 0 ? -(__int128)q : (__int128)q;
-              if (!WIDE &&
-                  (sq > (__int128)INT64_MAX || sq < (__int128)INT64_MIN)) {
-                atomicOr(d.errorFlag, kErrRetryWide);
-                bad = true;
-                break;
-              }
-              if (WIDE) {
-                Int128 rr = {(uint64_t)sq, (int64_t)(sq >> 64)};
-                v = *(typename VT<WIDE>::T*)&rr;
-              } else {
-                int64_t qq = (int64_t)sq;
-                v = *(typename VT<WIDE>::T*)&qq;
-              }
-            }
-          }
-          vm.set(ins.dst, v);
-          vm.setNull(ins.dst, nul);
-          break;
-        }
-        case VM_DIV: {
-          // DecimalDiv semantics (same as the fused DIVOK path): quotient
-          // truncated toward zero at the word-granular result scale;
-          // division by zero -> NULL
-          bool nul = vm.isNull(ins.a) || vm.isNull(ins.b);
-          typename VT<WIDE>::T v = VT<WIDE>::zero();
-          if (!nul) {
-            Int128 bi = VT<WIDE>::toAcc(vm.get(ins.b));
-            __int128 bv = ((__int128)bi.hi << 64) | (__int128)bi.lo;
-            if (bv == 0) {
-              nul = true;
-            } else {
-              Int128 ai = VT<WIDE>::toAcc(vm.get(ins.a));
-              __int128 av = ((__int128)ai.hi << 64) | (__int128)ai.lo;
-              int e = ins.c;
-              unsigned __int128 p10 =
-                  (unsigned __int128)(uint64_t)kP10(e > 18 ? 18 : e);
-              if (e > 18) p10 *= (uint64_t)kP10(e - 18);
-              unsigned __int128 aAbs = (unsigned __int128)(av < 0 ? -av : av);
-              unsigned __int128 lim =
-                  ((unsigned __int128)kDivArgMax[e][1] << 64) |
-                  kDivArgMax[e][0];
-              if (aAbs > lim) {
-                atomicOr(d.errorFlag, kErrOverflow);
-                bad = true;
-                break;
-              }
-              unsigned __int128 bAbs = (unsigned __int128)(bv < 0 ? -bv : bv);
-              unsigned __int128 num = aAbs * p10;
-              unsigned __int128 uq = (bAbs >> 64) != 0
-                                         ? u128DivBig(num, bAbs)
-                                         : u128DivU64(num, (uint64_t)bAbs);
-              bool negq = (av < 0) != (bv < 0);
-              __int128 q = negq ? -(__int128)uq : (__int128)uq;
-              if (!WIDE &&
-                  (q > (__int128)INT64_MAX || q < (__int128)INT64_MIN)) {
-                atomicOr(d.errorFlag, kErrRetryWide);
-                bad = true;
-                break;
-              }
-              if (WIDE) {
-                Int128 rr = {(uint64_t)q, (int64_t)(q >> 64)};
-                v = *(typename VT<WIDE>::T*)&rr;
-              } else {
-                int64_t qq = (int64_t)q;
-                v = *(typename VT<WIDE>::T*)&qq;
-              }
-            }
-          }
-          vm.set(ins.dst, v);
-          vm.setNull(ins.dst, nul);
-          break;
-        }
         default:
-          atomicOr(d.errorFlag, kErrBadDecimal);
-          bad = true;
+          if (!vmStep<WIDE, kVmOpsFull>(vm, ins, d.insP10[i], d.constLo,
+                                        d.constHi, d.errorFlag, &ovf))
+            bad = true;
           break;
       }
     }
