@@ -314,6 +314,12 @@ int64_t gx_last_sel_count(gx_exec* ex);
  * 0 while every decimal still reads the 40-byte form). */
 const char* gx_debug_jit_source(gx_exec* ex);
 int32_t gx_debug_dec_units_cols(gx_exec* ex);
+/* product engine only, debug (not part of the stable ABI): a text dump of the
+ * expression-VM program the plan compiled to -- site (fused / probe /
+ * projection), instruction stream with its precomputed constants, constants,
+ * fetch table, LIKE pattern count. Valid after gx_build, no GPU needed; the
+ * string is overwritten by the next call. */
+const char* gx_debug_vm_program(gx_exec* ex);
 
 /* ---- decimal helpers (each library's own implementation; used by golden
  * vector tests against pkg/types/mydecimal_test.go answers) ---- */

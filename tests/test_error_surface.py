@@ -158,3 +158,32 @@ def test_tuple_outside_distinct_rejected():
         return agg, src, _i64_chunk()
     _expect_error(plan, "tuple", "DISTINCT", "decimal",
                   "unsupported function")
+
+
+def test_decimal_frac_out_of_range_rejected():
+    """A decimal column wider than 9 fractional digits has no entry in the
+    load's power and reciprocal tables: a plan error at every VM site."""
+    def plan(b, lib):
+        src = b.source([GX_TYPE_I64, GX_TYPE_DECIMAL], [0, 12])
+        agg = b.hashagg(src, [b.colref(0, GX_TYPE_I64)],
+                        [(GX_AGG_SUM, b.colref(1, GX_TYPE_DECIMAL, 12), 12)])
+        ch = PyChunk([GX_TYPE_I64, GX_TYPE_DECIMAL], 1, [0, 12])
+        return agg, src, [ch]
+    _expect_error(plan, "scale out of range")
+
+
+def test_scale_shift_out_of_range_rejected():
+    """sum(k + a*b*c), a, b, c at frac 9: k scales up by 10^27, past the
+    19-entry power table."""
+    def plan(b, lib):
+        from tests.gxlib import GX_F_MUL, GX_F_PLUS
+        D = GX_TYPE_DECIMAL
+        src = b.source([GX_TYPE_I64, D, D, D, GX_TYPE_I64], [0, 9, 9, 9, 0])
+        ab = b.call(GX_F_MUL, D, 18, b.colref(1, D, 9), b.colref(2, D, 9))
+        abc = b.call(GX_F_MUL, D, 27, ab, b.colref(3, D, 9))
+        val = b.call(GX_F_PLUS, D, 27, b.colref(4, GX_TYPE_I64), abc)
+        agg = b.hashagg(src, [b.colref(0, GX_TYPE_I64)],
+                        [(GX_AGG_SUM, val, 27)])
+        ch = PyChunk([GX_TYPE_I64, D, D, D, GX_TYPE_I64], 1, [0, 9, 9, 9, 0])
+        return agg, src, [ch]
+    _expect_error(plan, "shift out of range")

@@ -57,8 +57,9 @@ def expected_q3(lib):
     return rows[:10]
 
 
-def run_q3(lib, limit=10):
-    b, (cust, orders, li), topn, out_types, out_fracs = P.q3_plan(lib, limit)
+def run_q3(lib, limit=10, wrap_revenue=None):
+    b, (cust, orders, li), topn, out_types, out_fracs = P.q3_plan(
+        lib, limit, wrap_revenue)
     ex = b.build(topn)
     ex.bind_tpch(cust, GX_TPCH_CUSTOMER, N_CUST)
     ex.bind_tpch(orders, GX_TPCH_ORDERS, N_ORD)

@@ -17,8 +17,8 @@ sum(expr) GROUP BY g through the generated kernel, the interpreter
 oracle is exact (decimals by value, NULL as NULL).
 
 Two things the sites themselves rule out:
-  * Projection's host compiler has no division, so `/` runs in the
-    aggregate cases only.
+  * Projection's opcode set on the host (kVmOpsProject, gx_engine.cpp) is
+    the full set without VM_DIV, so `/` runs in the aggregate cases only.
   * The oracle has no general LIKE. Its plan spells the same pattern,
     'ab%', with GX_F_LIKE_PREFIX; the product plan uses GX_F_LIKE, which is
     what lowers to VM_LIKE.
@@ -377,3 +377,41 @@ def test_q3_interpreted_probe(monkeypatch):
     want = run_q3(load_oracle())
     assert len(got) == len(want) > 0
     assert got == want
+
+
+@pytest.mark.gpu
+def test_q3_round_leaves_the_probe(monkeypatch, capfd):
+    """Q3 summing ROUND(price * (1 - disc), 2): VM_ROUND_SCALE is outside the
+    probe kernel's opcode set, so the host refuses the join-aggregate
+    pipeline and the plan runs as aggregation over joined rows. The TopN
+    limit exceeds the group count and rows compare sorted: two-digit
+    revenues tie."""
+    from tests.test_oracle_q3 import run_q3
+    _setenv(monkeypatch)
+    want = sorted(run_q3(load_oracle(), 100000, P.round_revenue))
+    capfd.readouterr()
+    got = sorted(run_q3(load_product(), 100000, P.round_revenue))
+    log = capfd.readouterr().err
+    assert len(want) > 50
+    assert got == want
+    assert "[gx] ja " not in log  # no join-aggregate build or probe ran
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("no_jit", [0, 1])
+def test_q3_if_value_on_the_probe(no_jit, monkeypatch, capfd):
+    """Q3 summing IF(disc > 0.05, price * (1 - disc), price): VM_CMP and
+    VM_IF keep their third operand in ins.c, which the probe's host site
+    must hand to the kernel as compiled. Generated and interpreted probe."""
+    from tests.test_oracle_q3 import run_q3
+    _setenv(monkeypatch, GX_NO_JIT=no_jit)
+    want = sorted(run_q3(load_oracle(), 100000, P.if_revenue))
+    capfd.readouterr()
+    got = sorted(run_q3(load_product(), 100000, P.if_revenue))
+    log = capfd.readouterr().err
+    assert len(want) > 50
+    assert got == want
+    # differs from plain Q3: the IF took effect
+    assert want != sorted(run_q3(load_oracle(), 100000))
+    if not no_jit:
+        assert "[gx] ja jit ok" in log

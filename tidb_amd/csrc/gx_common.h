@@ -280,11 +280,11 @@ struct FusedQueryDesc {
   int32_t accKind[kMaxAggs];
   int32_t accFcol[kMaxAggs];
   int32_t sharedCnt = 0;
-  int32_t hasDiv = 0;
+  int32_t hasDiv = 0;   // launch the DIVOK kernel variant (division code is
+                        // compiled out of the common kernels: its register
+                        // demand alone costs a wave/SIMD of occupancy)
   int32_t nVmRegs = 0;  // registers the compiled VM uses (>12 selects the
-                        // wide VmState14 kernel variant)  // launch the DIVOK kernel variant (division code is
-                       // compiled out of the common kernels: its register
-                       // demand alone costs a wave/SIMD of occupancy)
+                        // wide VmState14 kernel variant)
   GroupKeyDesc gkey;
   // outputs
   GroupSlot* globalTable = nullptr;  // 1<<globalGroupsLog2 slots

@@ -122,6 +122,162 @@ struct OutRowVal {
 
 }  // namespace
 
+struct gx_exec;
+
+// ---- host expression compiler: one for the fused, probe and projection
+// VMs ----
+// Projection's kernel runs the full step, but its host site has never lowered
+// division; enabling it there is a separate change.
+constexpr uint32_t kVmOpsProject = gxp::kVmOpsFull & ~(1u << gxp::VM_DIV);
+// the probe and projection kernels hold a 12-register VmState
+constexpr int kVmRegsNarrowState = 12;
+
+// Lowers PExpr trees to VmIns for one site (vmCompile). The site binds its
+// descriptor's program fields, the schema the expressions run over, the
+// opcode set its kernel executes and its register budget. Fetch slots are
+// never assigned here: loads carry c = -1.
+struct ExprBuilder {
+  // target program (the three descriptors share these field names)
+  gxp::VmIns* ins = nullptr;
+  int32_t* nIns = nullptr;
+  int64_t* constLo = nullptr;
+  int64_t* constHi = nullptr;
+  int32_t* nConsts = nullptr;
+  int64_t* insP10 = nullptr;
+  uint64_t* insMagic = nullptr;
+  int32_t* wide = nullptr;
+  gxp::LikePat* likePats = nullptr;  // VM_LIKE pattern table, if the site has one
+  int32_t* nLikePats = nullptr;
+  // schema the program runs over; colBase = plan colref index of its column 0
+  const std::vector<int>* colTypes = nullptr;
+  const std::vector<int>* colFracs = nullptr;
+  int colBase = 0;
+  uint32_t ops = 0;  // opcode set of the site's kernel (gxp::kVmOps*)
+  // registers: bump allocation up to maxRegs. With consumer counts
+  // (countConsumers) a derived value's register returns to the free list
+  // after its last consumer is emitted, so wide projections fit.
+  int maxRegs = 0;
+  int nextReg = 0;
+  bool recycle = false;
+  std::map<int, int> exprUse;  // remaining consumers per expression
+  std::vector<int> freeRegs;
+  std::map<int, std::pair<int, int>> memo;  // exprId -> (reg, scale)
+  bool hasDiv = false;  // DIV forces the wide VM and disables glds
+
+  template <class Desc>
+  void bind(Desc& d, const std::vector<int>* types,
+            const std::vector<int>* fracs, int base, uint32_t opSet, int regs) {
+    ins = d.ins;
+    nIns = &d.nIns;
+    constLo = d.constLo;
+    constHi = d.constHi;
+    nConsts = &d.nConsts;
+    insP10 = d.insP10;
+    insMagic = d.insMagic;
+    wide = &d.wide;
+    colTypes = types;
+    colFracs = fracs;
+    colBase = base;
+    ops = opSet;
+    maxRegs = regs;
+  }
+  template <class Desc>
+  void bindLikePats(Desc& d) {
+    likePats = d.likePats;
+    nLikePats = &d.nLikePats;
+  }
+
+  // Consumer counts over the expression DAG below `roots`; supplying them
+  // turns recycling on. Roots are pinned outputs: never counted, never
+  // released (a root may also appear as a subexpression, e.g. a projected
+  // value the cast of which is also projected).
+  void countConsumers(const PPlan& plan, const std::vector<int>& roots) {
+    std::set<int> visited;
+    std::function<void(int)> cnt = [&](int id) {
+      for (int a : plan.exprs[id].args) {
+        exprUse[a]++;
+        if (visited.insert(a).second) cnt(a);
+      }
+    };
+    for (int r : roots) cnt(r);
+    for (int r : roots) exprUse.erase(r);
+    recycle = true;
+  }
+
+  int allocReg() {
+    if (recycle && !freeRegs.empty()) {
+      int r = freeRegs.back();
+      freeRegs.pop_back();
+      return r;
+    }
+    return allocRegFresh();
+  }
+  // Loads are MOVED to the front of the instruction stream (the grouped
+  // fetch pipeline); a load's destination register must therefore never be
+  // a recycled one -- an instruction that originally preceded the load and
+  // wrote that register would execute after it post-reorder and clobber the
+  // loaded value. Fresh registers only for loads.
+  int allocRegFresh() {
+    if (nextReg >= maxRegs) {
+      if (getenv("GX_DEBUG"))
+        fprintf(stderr, "[gx] reg exhausted (nIns=%d, memo=%d)\n", *nIns,
+                (int)memo.size());
+      return -1;
+    }
+    return nextReg++;
+  }
+  // an anonymous scale-up temporary dies with the op that consumed it
+  void freeTemp(int reg) {
+    if (recycle && reg >= 0) freeRegs.push_back(reg);
+  }
+  // emitted the last consumer of argExpr -> recycle its register
+  void release(int argExpr) {
+    if (!recycle) return;
+    auto u = exprUse.find(argExpr);
+    if (u == exprUse.end()) return;  // pinned (projection root) or unknown
+    if (--u->second > 0) return;
+    auto c = memo.find(argExpr);
+    if (c == memo.end()) return;
+    // aliased entries (no-op casts) share a register: keep it live while
+    // any other expression still maps to it
+    for (auto& kv : memo)
+      if (kv.first != argExpr && kv.second.first == c->second.first) return;
+    // LOAD results must stay cached: the loads-first reorder hands their
+    // slots to the fetch pipeline once; recompiling one later would add a
+    // second load of the same column. Only recycle derived values.
+    int op = -1;
+    for (int i = 0; i < *nIns; i++)
+      if (ins[i].dst == c->second.first) op = ins[i].op;
+    if (op == gxp::VM_LOAD_DEC || op == gxp::VM_LOAD_I64 ||
+        op == gxp::VM_LOAD_CONST)
+      return;
+    freeRegs.push_back(c->second.first);
+    memo.erase(c);
+  }
+
+  // Screens `op` against the site's set: an opcode the site's kernel does
+  // not run is a plan error here, not a device error at run time.
+  bool allowed(gx_exec* ex, int op) const;
+  int emit(gx_exec* ex, int op, int dst, int a, int b, int c = -1) {
+    if (!allowed(ex, op)) return -1;
+    if (dst < 0 || *nIns >= gxp::kMaxVmIns) return -1;
+    ins[(*nIns)++] = {op, dst, a, b, c};
+    return dst;
+  }
+  // ra, rb at scales sa, sb -> both at max(sa, sb), the result frac of
+  // MySQL add/sub/compare/IF; tmpA/tmpB receive the scale-up temporaries
+  int alignScales(gx_exec* ex, int* ra, int sa, int* rb, int sb, int* tmpA,
+                  int* tmpB) {
+    int target = std::max(sa, sb);
+    *tmpA = *tmpB = -1;
+    if (sa < target)
+      *tmpA = *ra = emit(ex, gxp::VM_SCALE_UP, allocReg(), *ra, target - sa);
+    if (sb < target)
+      *tmpB = *rb = emit(ex, gxp::VM_SCALE_UP, allocReg(), *rb, target - sb);
+    return target;
+  }
+};
+
 struct gx_pb {
   PPlan plan;
 };
@@ -155,15 +311,7 @@ struct gx_exec {
   int sourceNode = -1;
   gxp::FusedQueryDesc desc;
   std::vector<std::pair<int, int>> projRegs;  // projection idx -> (reg, scale)
-  int vmNextReg = 0;
-  std::map<int, std::pair<int, int>> exprRegCache;  // exprId -> (reg, scale)
-  // register recycling: remaining consumer count per expression (computed
-  // from the projection roots before compiling); a subexpression's register
-  // returns to the free list after its last consumer is emitted, so wide
-  // projections fit the 12-register VM state
-  std::map<int, int> exprUse;
-  std::vector<int> vmFreeRegs;
-  bool vmHasDiv = false;  // DIV forces the wide VM and disables glds
+  ExprBuilder vm;  // fused expression compile state (reset by compileFused)
   // hipRTC-specialized kernel for this plan (gx_jit.cpp); nullptr -> use the
   // interpreted fusedAggKernel
   const gxjit::JitProg* jitProg = nullptr;
@@ -484,357 +632,17 @@ static int internLikePat(gx_exec* ex, gxp::LikePat* tab, int32_t* nTab,
   return (*nTab)++;
 }
 
-// compile expression exprId (over SOURCE columns) into the VM; returns reg or
-// -1 on error. *scaleOut = static scale of the value.
-static int compileExpr(gx_exec* ex, int exprId, int* scaleOut) {
-  gxp::FusedQueryDesc& d = ex->desc;
-  const PExpr& e = ex->plan.exprs[exprId];
-  auto cached = ex->exprRegCache.find(exprId);
-  if (cached != ex->exprRegCache.end()) {
-    *scaleOut = cached->second.second;
-    return cached->second.first;
+bool ExprBuilder::allowed(gx_exec* ex, int op) const {
+  if ((ops >> op) & 1) return true;
+  if (op == gxp::VM_LIKE) {
+    // a plan error, not a reason to fall back (gx_exec::jaLikeRejected)
+    ex->jaLikeRejected = true;
+    ex->err = "LIKE in value context is not supported in the "
+              "join-aggregate pipeline";
+  } else {
+    ex->err = "unsupported function on device path";
   }
-  auto allocReg = [&]() -> int {
-    if (!ex->vmFreeRegs.empty()) {
-      int r = ex->vmFreeRegs.back();
-      ex->vmFreeRegs.pop_back();
-      return r;
-    }
-    if (ex->vmNextReg >= gxp::kMaxVmRegs) {
-      if (getenv("GX_DEBUG"))
-        fprintf(stderr, "[gx] reg exhausted at expr %d (nIns=%d, cache=%d)\n",
-                exprId, d.nIns, (int)ex->exprRegCache.size());
-      return -1;
-    }
-    return ex->vmNextReg++;
-  };
-  auto emit = [&](int op, int dst, int a, int b) -> int {
-    if (dst < 0 || d.nIns >= gxp::kMaxVmIns) return -1;
-    d.ins[d.nIns++] = {op, dst, a, b, -1};
-    return dst;
-  };
-  // emitted the last consumer of argExpr -> recycle its register
-  auto release = [&](int argExpr) {
-    auto u = ex->exprUse.find(argExpr);
-    if (u == ex->exprUse.end()) {
-      if (getenv("GX_DEBUG"))
-        fprintf(stderr, "[gx] release %d: not counted (pinned)\n", argExpr);
-      return;  // pinned (projection root) or unknown
-    }
-    if (--u->second > 0) {
-      if (getenv("GX_DEBUG"))
-        fprintf(stderr, "[gx] release %d: %d uses left\n", argExpr, u->second);
-      return;
-    }
-    if (getenv("GX_DEBUG")) fprintf(stderr, "[gx] release %d: freeing\n", argExpr);
-    auto c = ex->exprRegCache.find(argExpr);
-    if (c != ex->exprRegCache.end()) {
-      // aliased entries (no-op casts) share a register: keep it live while
-      // any other expression still maps to it
-      for (auto& kv : ex->exprRegCache)
-        if (kv.first != argExpr && kv.second.first == c->second.first) return;
-      // LOAD results must stay cached: the loads-first reorder hands their
-      // slots to the fetch pipeline once; recompiling one later would add a
-      // second load of the same column. Only recycle derived values.
-      int op = -1;
-      for (int i2 = 0; i2 < d.nIns; i2++)
-        if (d.ins[i2].dst == c->second.first) op = d.ins[i2].op;
-      if (op == gxp::VM_LOAD_DEC || op == gxp::VM_LOAD_I64 ||
-          op == gxp::VM_LOAD_CONST)
-        return;
-      ex->vmFreeRegs.push_back(c->second.first);
-      ex->exprRegCache.erase(c);
-    }
-  };
-  // loads are MOVED to the front of the instruction stream (the grouped
-  // fetch pipeline); a load's destination register must therefore never be
-  // a recycled one -- an instruction that originally preceded the load and
-  // wrote that register would execute after it post-reorder and clobber the
-  // loaded value. Fresh registers only for loads.
-  auto allocRegFresh = [&]() -> int {
-    if (ex->vmNextReg >= gxp::kMaxVmRegs) {
-      if (getenv("GX_DEBUG"))
-        fprintf(stderr, "[gx] fresh reg exhausted at expr %d\n", exprId);
-      return -1;
-    }
-    return ex->vmNextReg++;
-  };
-  int reg = -1;
-  switch (e.kind) {
-    case EK_COLREF: {
-      if (e.colIdx < 0 || e.colIdx >= ex->desc.table.nCols) {
-        ex->err = "bad colref";
-        return -1;
-      }
-      int t = ex->desc.table.cols[e.colIdx].type;
-      if (t == GX_TYPE_DECIMAL) {
-        int frac = ex->desc.table.cols[e.colIdx].frac;
-        reg = emit(gxp::VM_LOAD_DEC, allocRegFresh(), e.colIdx, frac);
-        *scaleOut = frac;
-      } else if (t == GX_TYPE_I64) {
-        reg = emit(gxp::VM_LOAD_I64, allocRegFresh(), e.colIdx, 0);
-        *scaleOut = 0;
-      } else {
-        ex->err = "unsupported colref type in device expression";
-        return -1;
-      }
-      break;
-    }
-    case EK_CONST: {
-      __int128 u = 0;
-      int sc = 0;
-      if (e.retType == GX_TYPE_DECIMAL) {
-        if (!decToUnits(e.constDec, &u, &sc)) {
-          ex->err = "const decimal too wide for device path";
-          return -1;
-        }
-      } else if (e.retType == GX_TYPE_I64) {
-        u = e.constI64;
-        sc = 0;
-      } else {
-        ex->err = "unsupported const type in device expression";
-        return -1;
-      }
-      if (d.nConsts >= gxp::kMaxVmConsts) {
-        ex->err = "too many consts";
-        return -1;
-      }
-      int ci = d.nConsts++;
-      d.constLo[ci] = (int64_t)(uint64_t)u;
-      d.constHi[ci] = (int64_t)(u >> 64);
-      if (u > (__int128)INT64_MAX || u < (__int128)INT64_MIN)
-        ex->desc.wide = 1;  // narrow VM cannot hold this constant
-      reg = emit(gxp::VM_LOAD_CONST, allocReg(), ci, 0);
-      *scaleOut = sc;
-      break;
-    }
-    case EK_CALL: {
-      if (e.func == GX_F_LENGTH) {  // builtinLengthSig: byte length -> i64
-        if (e.args.size() != 1 ||
-            ex->plan.exprs[e.args[0]].kind != EK_COLREF) {
-          ex->err = "device LENGTH takes one string column";
-          return -1;
-        }
-        int col = ex->plan.exprs[e.args[0]].colIdx;
-        if (col < 0 || col >= ex->desc.table.nCols ||
-            ex->desc.table.cols[col].type != GX_TYPE_STRING) {
-          ex->err = "device LENGTH argument must be a string column";
-          return -1;
-        }
-        reg = emit(gxp::VM_STRLEN, allocRegFresh(), col, 0);
-        *scaleOut = 0;
-        break;
-      }
-      if (e.func == GX_F_LIKE || e.func == GX_F_NOT_LIKE) {
-        // LIKE in value context: i64 0/1, NULL when the string is NULL
-        std::vector<int> types(d.table.nCols);
-        for (int c = 0; c < d.table.nCols; c++) types[c] = d.table.cols[c].type;
-        gxp::LikePat lp;
-        int col;
-        if (!compileLikeCall(ex, e, types, 0, &col, &lp)) return -1;
-        int pi = internLikePat(ex, d.likePats, &d.nLikePats, lp);
-        if (pi < 0) return -1;
-        reg = emit(gxp::VM_LIKE, allocReg(), col, pi);
-        if (reg >= 0) d.ins[d.nIns - 1].c = e.func == GX_F_NOT_LIKE ? 1 : 0;
-        *scaleOut = 0;
-        break;
-      }
-      if (e.func == GX_F_CAST_DEC || e.func == GX_F_CAST_INT ||
-          e.func == GX_F_ROUND) {
-        int sr = -1;
-        if (e.func == GX_F_ROUND) {
-          if (e.args.size() != 2 ||
-              ex->plan.exprs[e.args[1]].kind != EK_CONST ||
-              ex->plan.exprs[e.args[1]].constI64 < 0) {
-            ex->err = "ROUND takes (expr, const d >= 0) this round";
-            return -1;
-          }
-          sr = (int)std::min<int64_t>(ex->plan.exprs[e.args[1]].constI64,
-                                      e.retFrac);
-        } else if (e.args.size() != 1) {
-          ex->err = "cast takes one argument";
-          return -1;
-        }
-        int sa = 0;
-        int ra = compileExpr(ex, e.args[0], &sa);
-        if (ra < 0) return -1;
-        if (sr < 0) sr = e.func == GX_F_CAST_INT ? 0 : e.retFrac;
-        if (sr == sa) {
-          reg = ra;  // no-op cast
-          *scaleOut = sr;
-          break;
-        }
-        reg = emit(gxp::VM_ROUND_SCALE, allocReg(), ra, sr);
-        if (reg >= 0) d.ins[d.nIns - 1].c = sa;
-        release(e.args[0]);
-        *scaleOut = sr;
-        break;
-      }
-      if (e.func == GX_F_ABS && e.args.size() == 1) {
-        int sa = 0;
-        int ra = compileExpr(ex, e.args[0], &sa);
-        if (ra < 0) return -1;
-        reg = emit(gxp::VM_ABS, allocReg(), ra, 0);
-        release(e.args[0]);
-        *scaleOut = sa;
-        break;
-      }
-      if (e.func == GX_F_IF && e.args.size() == 3) {
-        // builtinIfSig: branches scale-align; the cond keeps its own scale
-        int sc2 = 0, sa = 0, sb = 0;
-        int rc2 = compileExpr(ex, e.args[0], &sc2);
-        if (rc2 < 0) return -1;
-        int ra = compileExpr(ex, e.args[1], &sa);
-        if (ra < 0) return -1;
-        int rb = compileExpr(ex, e.args[2], &sb);
-        if (rb < 0) return -1;
-        int target = std::max(sa, sb);
-        int tmpA = -1, tmpB = -1;
-        if (sa < target) tmpA = ra = emit(gxp::VM_SCALE_UP, allocReg(), ra, target - sa);
-        if (sb < target) tmpB = rb = emit(gxp::VM_SCALE_UP, allocReg(), rb, target - sb);
-        if (ra < 0 || rb < 0) break;
-        reg = emit(gxp::VM_IF, allocReg(), rc2, ra);
-        if (reg >= 0) d.ins[d.nIns - 1].c = rb;
-        if (tmpA >= 0) ex->vmFreeRegs.push_back(tmpA);
-        if (tmpB >= 0) ex->vmFreeRegs.push_back(tmpB);
-        *scaleOut = target;
-        release(e.args[0]);
-        release(e.args[1]);
-        release(e.args[2]);
-        break;
-      }
-      if (e.func >= GX_F_YEAR && e.func <= GX_F_SECOND) {
-        // YEAR/MONTH/DAY: raw CoreTime bits load (nulls tracked by the
-        // load) + bitfield extract; only direct TIME columns this round
-        const PExpr* a0 =
-            e.args.size() == 1 ? &ex->plan.exprs[e.args[0]] : nullptr;
-        if (!a0 || a0->kind != EK_COLREF || a0->colIdx < 0 ||
-            a0->colIdx >= ex->desc.table.nCols ||
-            ex->desc.table.cols[a0->colIdx].type != GX_TYPE_TIME) {
-          ex->err = "YEAR/MONTH/DAY take a time column";
-          return -1;
-        }
-        int lr = emit(gxp::VM_LOAD_I64, allocRegFresh(), a0->colIdx, 0);
-        if (lr < 0) break;
-        reg = emit(gxp::VM_TIME_EXTRACT, allocReg(), lr, e.func - GX_F_YEAR);
-        *scaleOut = 0;
-        break;
-      }
-      if (e.args.size() != 2) {
-        ex->err = "unsupported call arity on device";
-        return -1;
-      }
-      int sa = 0, sb = 0;
-      int ra = compileExpr(ex, e.args[0], &sa);
-      if (ra < 0) return -1;
-      int rb = compileExpr(ex, e.args[1], &sb);
-      if (rb < 0) return -1;
-      if (e.func == GX_F_IFNULL || e.func == GX_F_GREATEST ||
-          e.func == GX_F_LEAST || e.func <= GX_F_NE) {
-        // builtinIfNullSig / builtinGreatest*Sig / builtinLeast*Sig, and
-        // the compare family in VALUE context (i64 0/1, NULL on NULL):
-        // align operand scales; compares emit VM_CMP with the op in .c
-        int op2 = e.func <= GX_F_NE
-                      ? gxp::VM_CMP
-                      : e.func == GX_F_IFNULL
-                            ? gxp::VM_IFNULL
-                            : (e.func == GX_F_GREATEST ? gxp::VM_MAX2
-                                                       : gxp::VM_MIN2);
-        int target = std::max(sa, sb);
-        int tmpA = -1, tmpB = -1;
-        if (sa < target) tmpA = ra = emit(gxp::VM_SCALE_UP, allocReg(), ra, target - sa);
-        if (sb < target) tmpB = rb = emit(gxp::VM_SCALE_UP, allocReg(), rb, target - sb);
-        if (ra < 0 || rb < 0) break;
-        reg = emit(op2, allocReg(), ra, rb);
-        if (reg >= 0 && op2 == gxp::VM_CMP) d.ins[d.nIns - 1].c = e.func;
-        if (tmpA >= 0) ex->vmFreeRegs.push_back(tmpA);
-        if (tmpB >= 0) ex->vmFreeRegs.push_back(tmpB);
-        *scaleOut = op2 == gxp::VM_CMP ? 0 : target;
-        release(e.args[0]);
-        release(e.args[1]);
-        break;
-      }
-      int op;
-      switch (e.func) {
-        case GX_F_PLUS: op = gxp::VM_ADD; break;
-        case GX_F_MINUS: op = gxp::VM_SUB; break;
-        case GX_F_MUL: op = gxp::VM_MUL; break;
-        case GX_F_DIV: op = gxp::VM_DIV; break;
-        default:
-          ex->err = "unsupported function on device path";
-          return -1;
-      }
-      if (op == gxp::VM_DIV) {
-        // result scale is word-granular (doDiv, mydecimal.go:1170-1215):
-        // frac_i word-rounded, fracIncr reduced by the slack, result frac =
-        // words(frac1w + frac2w + incr) * 9
-        int f1w = (sa + 8) / 9 * 9;
-        int f2w = (sb + 8) / 9 * 9;
-        int incr = std::max(0, 4 - (f1w - sa) - (f2w - sb));
-        int sr = (f1w + f2w + incr + 8) / 9 * 9;
-        if (sr > 30) sr = 30;
-        int e10 = sb + (sr - sa);
-        if (e10 < 0 || e10 > 36) {
-          ex->err = "division scale out of device range";
-          return -1;
-        }
-        reg = emit(op, allocReg(), ra, rb);
-        if (reg >= 0) d.ins[d.nIns - 1].c = e10;
-        ex->vmHasDiv = true;
-        *scaleOut = sr;
-      } else if (op == gxp::VM_MUL) {
-        reg = emit(op, allocReg(), ra, rb);
-        *scaleOut = sa + sb;
-      } else {
-        // align scales to max (MySQL add/sub result frac = max(f1,f2))
-        int target = std::max(sa, sb);
-        int tmpA = -1, tmpB = -1;
-        if (sa < target) tmpA = ra = emit(gxp::VM_SCALE_UP, allocReg(), ra, target - sa);
-        if (sb < target) tmpB = rb = emit(gxp::VM_SCALE_UP, allocReg(), rb, target - sb);
-        if (ra < 0 || rb < 0) break;
-        reg = emit(op, allocReg(), ra, rb);
-        // anonymous scale-up temps die with this op
-        if (tmpA >= 0) ex->vmFreeRegs.push_back(tmpA);
-        if (tmpB >= 0) ex->vmFreeRegs.push_back(tmpB);
-        *scaleOut = target;
-      }
-      release(e.args[0]);
-      release(e.args[1]);
-      break;
-    }
-  }
-  if (reg < 0 && ex->err.empty()) ex->err = "expression too large for device VM";
-  if (reg >= 0) ex->exprRegCache[exprId] = {reg, *scaleOut};
-  return reg;
-}
-
-// generic VM program build context (used by the fused-agg compiler and the
-// join-agg probe compiler)
-struct VmBuild {
-  gxp::VmIns* ins;
-  int32_t* nIns;
-  int64_t* cLo;
-  int64_t* cHi;
-  int32_t* nConsts;
-  gxp::FetchDesc* fetch;
-  int32_t* nFetch;
-  const std::vector<int>* colTypes;  // schema of the table the VM runs over
-  const std::vector<int>* colFracs;
-  int colBase = 0;  // plan colref index of this table's first column
-  int nextReg = 0;
-  std::map<int, std::pair<int, int>> cache;
-  int32_t* wideFlag;
-  // VM_LIKE pattern table of the target desc (null: no value-context LIKE)
-  gxp::LikePat* likePats = nullptr;
-  int32_t* nLikePats = nullptr;
-};
-
-static int vmFetchSlot(VmBuild& B, int kind, int col) {
-  for (int i = 0; i < *B.nFetch; i++)
-    if (B.fetch[i].kind == kind && B.fetch[i].col == col) return i;
-  if (*B.nFetch >= gxp::kMaxFetch) return -1;
-  B.fetch[*B.nFetch] = {kind, col};
-  return (*B.nFetch)++;
+  return false;
 }
 
 // allocate (or reuse) a raw-fetch slot for (kind, col) on the fused desc
@@ -847,43 +655,35 @@ static int fetchSlot(gx_exec* ex, int kind, int col) {
   return d.nFetch++;
 }
 
-// compile expression exprId over a single table schema into a VM program.
-// Returns the result register (>= 0) or -1; *scaleOut = static decimal scale.
-static int vmCompile(gx_exec* ex, VmBuild& B, int exprId, int* scaleOut) {
+// compile expression exprId over B's schema into B's VM program. Returns the
+// result register (>= 0) or -1; *scaleOut = static decimal scale of the value.
+static int vmCompile(gx_exec* ex, ExprBuilder& B, int exprId, int* scaleOut) {
   const PExpr& e = ex->plan.exprs[exprId];
-  auto cached = B.cache.find(exprId);
-  if (cached != B.cache.end()) {
+  auto cached = B.memo.find(exprId);
+  if (cached != B.memo.end()) {
     *scaleOut = cached->second.second;
     return cached->second.first;
   }
-  auto allocReg = [&]() -> int {
-    if (B.nextReg >= 12) return -1;  // the probe kernel's VmState is 12-reg
-    return B.nextReg++;
-  };
-  auto emit = [&](int op, int dst, int a, int b, int c) -> int {
-    if (dst < 0 || *B.nIns >= gxp::kMaxVmIns) return -1;
-    B.ins[(*B.nIns)++] = {op, dst, a, b, c};
-    return dst;
+  // schema column of a colref expression, or -1
+  auto colOf = [&](const PExpr& x) -> int {
+    int col = x.kind == EK_COLREF ? x.colIdx - B.colBase : -1;
+    return col >= 0 && col < (int)B.colTypes->size() ? col : -1;
   };
   int reg = -1;
   switch (e.kind) {
     case EK_COLREF: {
-      int col = e.colIdx - B.colBase;
-      if (col < 0 || col >= (int)B.colTypes->size()) {
+      int col = colOf(e);
+      if (col < 0) {
         ex->err = "bad colref in device expression";
         return -1;
       }
       int t = (*B.colTypes)[col];
       if (t == GX_TYPE_DECIMAL) {
         int frac = (*B.colFracs)[col];
-        int slot = vmFetchSlot(B, gxp::FETCH_DEC16, col);
-        if (slot < 0) { ex->err = "fetch plan full"; return -1; }
-        reg = emit(gxp::VM_LOAD_DEC, allocReg(), col, frac, slot);
+        reg = B.emit(ex, gxp::VM_LOAD_DEC, B.allocRegFresh(), col, frac);
         *scaleOut = frac;
       } else if (t == GX_TYPE_I64) {
-        int slot = vmFetchSlot(B, gxp::FETCH_8B, col);
-        if (slot < 0) { ex->err = "fetch plan full"; return -1; }
-        reg = emit(gxp::VM_LOAD_I64, allocReg(), col, 0, slot);
+        reg = B.emit(ex, gxp::VM_LOAD_I64, B.allocRegFresh(), col, 0);
         *scaleOut = 0;
       } else {
         ex->err = "unsupported colref type in device expression";
@@ -911,10 +711,11 @@ static int vmCompile(gx_exec* ex, VmBuild& B, int exprId, int* scaleOut) {
         return -1;
       }
       int ci = (*B.nConsts)++;
-      B.cLo[ci] = (int64_t)(uint64_t)u;
-      B.cHi[ci] = (int64_t)(u >> 64);
-      if (u > (__int128)INT64_MAX || u < (__int128)INT64_MIN) *B.wideFlag = 1;
-      reg = emit(gxp::VM_LOAD_CONST, allocReg(), ci, 0, -1);
+      B.constLo[ci] = (int64_t)(uint64_t)u;
+      B.constHi[ci] = (int64_t)(u >> 64);
+      if (u > (__int128)INT64_MAX || u < (__int128)INT64_MIN)
+        *B.wide = 1;  // narrow VM cannot hold this constant
+      reg = B.emit(ex, gxp::VM_LOAD_CONST, B.allocReg(), ci, 0);
       *scaleOut = sc;
       break;
     }
@@ -925,32 +726,26 @@ static int vmCompile(gx_exec* ex, VmBuild& B, int exprId, int* scaleOut) {
           ex->err = "device LENGTH takes one string column";
           return -1;
         }
-        int col = ex->plan.exprs[e.args[0]].colIdx - B.colBase;
-        if (col < 0 || col >= (int)B.colTypes->size() ||
-            (*B.colTypes)[col] != GX_TYPE_STRING) {
+        int col = colOf(ex->plan.exprs[e.args[0]]);
+        if (col < 0 || (*B.colTypes)[col] != GX_TYPE_STRING) {
           ex->err = "device LENGTH argument must be a string column";
           return -1;
         }
-        reg = emit(gxp::VM_STRLEN, allocReg(), col, 0, -1);
+        reg = B.emit(ex, gxp::VM_STRLEN, B.allocRegFresh(), col, 0);
         *scaleOut = 0;
         break;
       }
       if (e.func == GX_F_LIKE || e.func == GX_F_NOT_LIKE) {
         // LIKE in value context: i64 0/1, NULL when the string is NULL
-        if (!B.likePats) {
-          ex->jaLikeRejected = true;
-          ex->err = "LIKE in value context is not supported in the "
-                    "join-aggregate pipeline";
-          return -1;
-        }
+        if (!B.allowed(ex, gxp::VM_LIKE)) return -1;
         gxp::LikePat lp;
         int col;
         if (!compileLikeCall(ex, e, *B.colTypes, B.colBase, &col, &lp))
           return -1;
         int pi = internLikePat(ex, B.likePats, B.nLikePats, lp);
         if (pi < 0) return -1;
-        reg = emit(gxp::VM_LIKE, allocReg(), col, pi,
-                   e.func == GX_F_NOT_LIKE ? 1 : 0);
+        reg = B.emit(ex, gxp::VM_LIKE, B.allocReg(), col, pi,
+                     e.func == GX_F_NOT_LIKE ? 1 : 0);
         *scaleOut = 0;
         break;
       }
@@ -978,54 +773,55 @@ static int vmCompile(gx_exec* ex, VmBuild& B, int exprId, int* scaleOut) {
         int sa = 0;
         int ra = vmCompile(ex, B, e.args[0], &sa);
         if (ra < 0) return -1;
+        *scaleOut = sr;
         if (sr == sa) {
-          reg = ra;  // no-op cast
-          *scaleOut = sr;
+          reg = ra;  // no-op cast: aliases the argument's register
           break;
         }
-        reg = emit(gxp::VM_ROUND_SCALE, allocReg(), ra, sr, sa);
-        *scaleOut = sr;
+        reg = B.emit(ex, gxp::VM_ROUND_SCALE, B.allocReg(), ra, sr, sa);
+        B.release(e.args[0]);
         break;
       }
       if (e.func == GX_F_ABS && e.args.size() == 1) {
         int sa = 0;
         int ra = vmCompile(ex, B, e.args[0], &sa);
         if (ra < 0) return -1;
-        reg = emit(gxp::VM_ABS, allocReg(), ra, 0, -1);
+        reg = B.emit(ex, gxp::VM_ABS, B.allocReg(), ra, 0);
+        B.release(e.args[0]);
         *scaleOut = sa;
         break;
       }
       if (e.func == GX_F_IF && e.args.size() == 3) {
-        int sc2 = 0, sa = 0, sb = 0;
+        // builtinIfSig: branches scale-align; the cond keeps its own scale
+        int sc2 = 0, sa = 0, sb = 0, tmpA, tmpB;
         int rc2 = vmCompile(ex, B, e.args[0], &sc2);
         if (rc2 < 0) return -1;
         int ra = vmCompile(ex, B, e.args[1], &sa);
         if (ra < 0) return -1;
         int rb = vmCompile(ex, B, e.args[2], &sb);
         if (rb < 0) return -1;
-        int target = std::max(sa, sb);
-        if (sa < target) ra = emit(gxp::VM_SCALE_UP, allocReg(), ra, target - sa, -1);
-        if (sb < target) rb = emit(gxp::VM_SCALE_UP, allocReg(), rb, target - sb, -1);
+        *scaleOut = B.alignScales(ex, &ra, sa, &rb, sb, &tmpA, &tmpB);
         if (ra < 0 || rb < 0) break;
-        reg = emit(gxp::VM_IF, allocReg(), rc2, ra, rb);
-        *scaleOut = target;
+        reg = B.emit(ex, gxp::VM_IF, B.allocReg(), rc2, ra, rb);
+        B.freeTemp(tmpA);
+        B.freeTemp(tmpB);
+        B.release(e.args[0]);
+        B.release(e.args[1]);
+        B.release(e.args[2]);
         break;
       }
       if (e.func >= GX_F_YEAR && e.func <= GX_F_SECOND) {
-        const PExpr* a0 =
-            e.args.size() == 1 ? &ex->plan.exprs[e.args[0]] : nullptr;
-        int col = a0 && a0->kind == EK_COLREF ? a0->colIdx - B.colBase : -1;
-        if (col < 0 || col >= (int)B.colTypes->size() ||
-            (*B.colTypes)[col] != GX_TYPE_TIME) {
+        // YEAR..SECOND: raw CoreTime bits load (nulls tracked by the load) +
+        // bitfield extract; only direct TIME columns this round
+        int col = e.args.size() == 1 ? colOf(ex->plan.exprs[e.args[0]]) : -1;
+        if (col < 0 || (*B.colTypes)[col] != GX_TYPE_TIME) {
           ex->err = "YEAR/MONTH/DAY take a time column";
           return -1;
         }
-        int slot = vmFetchSlot(B, gxp::FETCH_8B, col);
-        if (slot < 0) { ex->err = "fetch plan full"; return -1; }
-        int lr = emit(gxp::VM_LOAD_I64, allocReg(), col, 0, slot);
+        int lr = B.emit(ex, gxp::VM_LOAD_I64, B.allocRegFresh(), col, 0);
         if (lr < 0) break;
-        reg = emit(gxp::VM_TIME_EXTRACT, allocReg(), lr, e.func - GX_F_YEAR,
-                   -1);
+        reg = B.emit(ex, gxp::VM_TIME_EXTRACT, B.allocReg(), lr,
+                     e.func - GX_F_YEAR);
         *scaleOut = 0;
         break;
       }
@@ -1033,54 +829,127 @@ static int vmCompile(gx_exec* ex, VmBuild& B, int exprId, int* scaleOut) {
         ex->err = "unsupported call arity on device";
         return -1;
       }
-      int sa = 0, sb = 0;
+      int sa = 0, sb = 0, tmpA, tmpB;
       int ra = vmCompile(ex, B, e.args[0], &sa);
       if (ra < 0) return -1;
       int rb = vmCompile(ex, B, e.args[1], &sb);
       if (rb < 0) return -1;
       if (e.func == GX_F_IFNULL || e.func == GX_F_GREATEST ||
           e.func == GX_F_LEAST || e.func <= GX_F_NE) {
+        // builtinIfNullSig / builtinGreatest*Sig / builtinLeast*Sig, and
+        // the compare family in VALUE context (i64 0/1, NULL on NULL):
+        // align operand scales; compares emit VM_CMP with the op in .c
         int op2 = e.func <= GX_F_NE
                       ? gxp::VM_CMP
                       : e.func == GX_F_IFNULL
                             ? gxp::VM_IFNULL
                             : (e.func == GX_F_GREATEST ? gxp::VM_MAX2
                                                        : gxp::VM_MIN2);
-        int target = std::max(sa, sb);
-        if (sa < target) ra = emit(gxp::VM_SCALE_UP, allocReg(), ra, target - sa, -1);
-        if (sb < target) rb = emit(gxp::VM_SCALE_UP, allocReg(), rb, target - sb, -1);
+        int target = B.alignScales(ex, &ra, sa, &rb, sb, &tmpA, &tmpB);
         if (ra < 0 || rb < 0) break;
-        reg = emit(op2, allocReg(), ra, rb,
-                   op2 == gxp::VM_CMP ? e.func : -1);
+        reg = B.emit(ex, op2, B.allocReg(), ra, rb,
+                     op2 == gxp::VM_CMP ? e.func : -1);
+        B.freeTemp(tmpA);
+        B.freeTemp(tmpB);
         *scaleOut = op2 == gxp::VM_CMP ? 0 : target;
-        break;
-      }
-      int op;
-      switch (e.func) {
-        case GX_F_PLUS: op = gxp::VM_ADD; break;
-        case GX_F_MINUS: op = gxp::VM_SUB; break;
-        case GX_F_MUL: op = gxp::VM_MUL; break;
-        default:
-          ex->err = "unsupported function on device path";
+      } else if (e.func == GX_F_DIV) {
+        if (!B.allowed(ex, gxp::VM_DIV)) return -1;
+        // result scale is word-granular (doDiv, mydecimal.go:1170-1215):
+        // frac_i word-rounded, fracIncr reduced by the slack, result frac =
+        // words(frac1w + frac2w + incr) * 9
+        int f1w = (sa + 8) / 9 * 9;
+        int f2w = (sb + 8) / 9 * 9;
+        int incr = std::max(0, 4 - (f1w - sa) - (f2w - sb));
+        int sr = (f1w + f2w + incr + 8) / 9 * 9;
+        if (sr > 30) sr = 30;
+        int e10 = sb + (sr - sa);
+        if (e10 < 0 || e10 > 36) {
+          ex->err = "division scale out of device range";
           return -1;
-      }
-      if (op == gxp::VM_MUL) {
-        reg = emit(op, allocReg(), ra, rb, -1);
+        }
+        reg = B.emit(ex, gxp::VM_DIV, B.allocReg(), ra, rb, e10);
+        B.hasDiv = true;
+        *scaleOut = sr;
+      } else if (e.func == GX_F_MUL) {
+        reg = B.emit(ex, gxp::VM_MUL, B.allocReg(), ra, rb);
         *scaleOut = sa + sb;
-      } else {
-        int target = std::max(sa, sb);
-        if (sa < target) ra = emit(gxp::VM_SCALE_UP, allocReg(), ra, target - sa, -1);
-        if (sb < target) rb = emit(gxp::VM_SCALE_UP, allocReg(), rb, target - sb, -1);
+      } else if (e.func == GX_F_PLUS || e.func == GX_F_MINUS) {
+        // align scales to max (MySQL add/sub result frac = max(f1,f2))
+        *scaleOut = B.alignScales(ex, &ra, sa, &rb, sb, &tmpA, &tmpB);
         if (ra < 0 || rb < 0) break;
-        reg = emit(op, allocReg(), ra, rb, -1);
-        *scaleOut = target;
+        reg = B.emit(ex, e.func == GX_F_PLUS ? gxp::VM_ADD : gxp::VM_SUB,
+                     B.allocReg(), ra, rb);
+        B.freeTemp(tmpA);
+        B.freeTemp(tmpB);
+      } else {
+        ex->err = "unsupported function on device path";
+        return -1;
       }
+      B.release(e.args[0]);
+      B.release(e.args[1]);
       break;
     }
   }
   if (reg < 0 && ex->err.empty()) ex->err = "expression too large for device VM";
-  if (reg >= 0) B.cache[exprId] = {reg, *scaleOut};
+  if (reg >= 0) B.memo[exprId] = {reg, *scaleOut};
   return reg;
+}
+
+// What a load-reordering site moves to the front of its stream.
+constexpr uint32_t kVmLoadOps = 1u << gxp::VM_LOAD_DEC | 1u << gxp::VM_LOAD_I64;
+
+// The finishing step of every VM site. Moves the instructions whose opcode
+// is in `frontOps` to the front of the stream, keeping their order (each dst
+// is written once and loads have no dependencies), then fills the
+// per-instruction constants insP10 / insMagic and range-checks what indexes
+// the tables. Returns the number of instructions moved to the front, or -1
+// with ex->err set.
+static int finishVmProgram(gx_exec* ex, ExprBuilder& B, uint32_t frontOps) {
+  static const int64_t p10h[19] = {1, 10, 100, 1000, 10000, 100000, 1000000,
+                                   10000000, 100000000, 1000000000,
+                                   10000000000LL, 100000000000LL,
+                                   1000000000000LL, 10000000000000LL,
+                                   100000000000000LL, 1000000000000000LL,
+                                   10000000000000000LL, 100000000000000000LL,
+                                   1000000000000000000LL};
+  // ceil(2^62 / 10^(9-f)) at index 9-f
+  static const uint64_t magich[10] = {
+      4611686018427387904ULL, 461168601842738791ULL, 46116860184273880ULL,
+      4611686018427388ULL,    461168601842739ULL,    46116860184274ULL,
+      4611686018428ULL,       461168601843ULL,       46116860185ULL,
+      4611686019ULL};
+  int n = *B.nIns;
+  gxp::VmIns* front = std::stable_partition(
+      B.ins, B.ins + n,
+      [&](const gxp::VmIns& in) { return (frontOps >> in.op) & 1; });
+  for (int i = 0; i < n; i++) {
+    const gxp::VmIns& in = B.ins[i];
+    B.insP10[i] = 1;
+    B.insMagic[i] = 0;
+    if (in.op == gxp::VM_LOAD_DEC) {
+      if (in.b < 0 || in.b > 9) {
+        ex->err = "decimal scale out of range (frac must be 0..9, got " +
+                  std::to_string(in.b) + ")";
+        return -1;
+      }
+      B.insP10[i] = p10h[in.b];
+      B.insMagic[i] = magich[9 - in.b];
+    } else if (in.op == gxp::VM_SCALE_UP) {
+      if (in.b < 0 || in.b > 18) {
+        ex->err = "scale shift out of range";
+        return -1;
+      }
+      B.insP10[i] = p10h[in.b];
+    } else if (in.op == gxp::VM_ROUND_SCALE) {
+      int sh = in.b - in.c;
+      if (sh < -18 || sh > 18) {
+        ex->err = "rescale shift out of range";
+        return -1;
+      }
+      B.insP10[i] = p10h[sh >= 0 ? sh : -sh];
+    }
+  }
+  return (int)(front - B.ins);
 }
 
 // compile one Selection condition over a single-table schema into a PredDesc
@@ -1418,19 +1287,11 @@ static int32_t compileJoinAgg(gx_exec* ex) {
     else ex->jaGroupType.push_back(ordN.colTypes[ja.payloadCol1]);
   }
 
-  // value expression VM over the probe (lineitem) table
-  VmBuild B;
-  B.ins = ja.ins;
-  B.nIns = &ja.nIns;
-  B.cLo = ja.constLo;
-  B.cHi = ja.constHi;
-  B.nConsts = &ja.nConsts;
-  B.fetch = ja.fetch;
-  B.nFetch = &ja.nFetch;
-  B.colTypes = &liN.colTypes;
-  B.colFracs = &liN.colFracs;
-  B.colBase = nc + no;
-  B.wideFlag = &ja.wide;
+  // value expression VM over the probe (lineitem) table; the probe kernel
+  // runs the core opcode set
+  ExprBuilder B;
+  B.bind(ja, &liN.colTypes, &liN.colFracs, nc + no, gxp::kVmOpsCore,
+         kVmRegsNarrowState);
   int sc = 0;
   int reg = vmCompile(ex, B, valueExpr, &sc);
   if (reg < 0) return GX_ERR_INVALID;
@@ -1439,42 +1300,15 @@ static int32_t compileJoinAgg(gx_exec* ex) {
   // lazy value loads: only the FILTER column is prefetched — the VM runs
   // only for rows that pass the filter AND hit the hash table (a small
   // fraction), so its columns are loaded at use (ins.c = -1)
-  ja.nFetch = 0;
-  for (int i = 0; i < ja.nIns; i++) ja.ins[i].c = -1;
   if (ja.nPredP &&
       (ja.predP.kind == gxp::PRED_TIME_CMP_CONST ||
-       ja.predP.kind == gxp::PRED_I64_CMP_CONST))
-    ja.predP.slot = vmFetchSlot(B, gxp::FETCH_8B, ja.predP.col);
-  // reorder loads first (mirrors the fused path)
-  {
-    std::vector<gxp::VmIns> loads, rest;
-    for (int i = 0; i < ja.nIns; i++) {
-      if (ja.ins[i].op == gxp::VM_LOAD_DEC || ja.ins[i].op == gxp::VM_LOAD_I64)
-        loads.push_back(ja.ins[i]);
-      else
-        rest.push_back(ja.ins[i]);
-    }
-    int k = 0;
-    for (auto& ins : loads) ja.ins[k++] = ins;
-    for (auto& ins : rest) ja.ins[k++] = ins;
-    static const int64_t p10h[10] = {1, 10, 100, 1000, 10000, 100000, 1000000,
-                                     10000000, 100000000, 1000000000};
-    static const uint64_t magich[10] = {
-        4611686018427387904ULL, 461168601842738791ULL, 46116860184273880ULL,
-        4611686018427388ULL,    461168601842739ULL,    46116860184274ULL,
-        4611686018428ULL,       461168601843ULL,       46116860185ULL,
-        4611686019ULL};
-    for (int i = 0; i < ja.nIns; i++) {
-      ja.insP10[i] = 1;
-      ja.insMagic[i] = 0;
-      if (ja.ins[i].op == gxp::VM_LOAD_DEC) {
-        ja.insP10[i] = p10h[ja.ins[i].b];
-        ja.insMagic[i] = magich[9 - ja.ins[i].b];
-      } else if (ja.ins[i].op == gxp::VM_SCALE_UP) {
-        ja.insP10[i] = p10h[ja.ins[i].b];
-      }
-    }
+       ja.predP.kind == gxp::PRED_I64_CMP_CONST)) {
+    ja.fetch[0] = {gxp::FETCH_8B, ja.predP.col};
+    ja.nFetch = 1;
+    ja.predP.slot = 0;
   }
+  // loads first (mirrors the fused path)
+  if (finishVmProgram(ex, B, kVmLoadOps) < 0) return GX_ERR_INVALID;
 
   // topn keys -> positions in the agg output row [groups..., sum]
   ex->jaSortKeys.clear();
@@ -1882,24 +1716,9 @@ static int32_t compileProject(gx_exec* ex) {
     return GX_ERR_INVALID;
   }
   gxp::ProjDesc& pd = ex->pd;
-  // the projection kernel loads directly (no fetch pipeline); give vmCompile
-  // a scratch fetch plan it can fill and we discard
-  gxp::FetchDesc scratchFetch[gxp::kMaxFetch];
-  int32_t scratchNFetch = 0;
-  VmBuild B;
-  B.ins = pd.ins;
-  B.nIns = &pd.nIns;
-  B.cLo = pd.constLo;
-  B.cHi = pd.constHi;
-  B.nConsts = &pd.nConsts;
-  B.fetch = scratchFetch;
-  B.nFetch = &scratchNFetch;
-  B.colTypes = childTypes;
-  B.colFracs = childFracs;
-  B.colBase = 0;
-  B.wideFlag = &pd.wide;
-  B.likePats = pd.likePats;
-  B.nLikePats = &pd.nLikePats;
+  ExprBuilder B;
+  B.bind(pd, childTypes, childFracs, 0, kVmOpsProject, kVmRegsNarrowState);
+  B.bindLikePats(pd);
   for (int eid : pj.exprs) {
     const PExpr& e = plan.exprs[eid];
     if (e.kind == EK_COLREF) {
@@ -1946,61 +1765,9 @@ static int32_t compileProject(gx_exec* ex) {
       ex->projOutFracs.push_back(outType == GX_TYPE_I64 ? 0 : sc);
     }
   }
-  // per-instruction precomputed constants (same rules as the fused path)
-  static const int64_t p10h[19] = {1,
-                                   10,
-                                   100,
-                                   1000,
-                                   10000,
-                                   100000,
-                                   1000000,
-                                   10000000,
-                                   100000000,
-                                   1000000000,
-                                   10000000000LL,
-                                   100000000000LL,
-                                   1000000000000LL,
-                                   10000000000000LL,
-                                   100000000000000LL,
-                                   1000000000000000LL,
-                                   10000000000000000LL,
-                                   100000000000000000LL,
-                                   1000000000000000000LL};
-  static const uint64_t magich[10] = {
-      4611686018427387904ULL, 461168601842738791ULL, 46116860184273880ULL,
-      4611686018427388ULL,    461168601842739ULL,    46116860184274ULL,
-      4611686018428ULL,       461168601843ULL,       46116860185ULL,
-      4611686019ULL};
-  for (int i = 0; i < pd.nIns; i++) {
-    pd.insP10[i] = 1;
-    pd.insMagic[i] = 0;
-    if (pd.ins[i].op == gxp::VM_LOAD_DEC) {
-      if (pd.ins[i].b < 0 || pd.ins[i].b > 9) {
-        ex->err = "decimal scale out of range for projection (frac must be "
-                  "0..9, got " + std::to_string(pd.ins[i].b) + ")";
-        return GX_ERR_INVALID;
-      }
-      pd.insP10[i] = p10h[pd.ins[i].b];
-      pd.insMagic[i] = magich[9 - pd.ins[i].b];
-    } else if (pd.ins[i].op == gxp::VM_SCALE_UP) {
-      if (pd.ins[i].b < 0 || pd.ins[i].b > 18) {
-        ex->err = "scale shift out of range for projection";
-        return GX_ERR_INVALID;
-      }
-      pd.insP10[i] = p10h[pd.ins[i].b];
-    } else if (pd.ins[i].op == gxp::VM_ROUND_SCALE) {
-      int sh = pd.ins[i].b - pd.ins[i].c;
-      if (sh < -18 || sh > 18) {
-        ex->err = "rescale shift out of range for projection";
-        return GX_ERR_INVALID;
-      }
-      pd.insP10[i] = p10h[sh >= 0 ? sh : -sh];
-    }
-  }
-  // loads use the direct path (no fetch slots in the projection kernel)
-  for (int i = 0; i < pd.nIns; i++)
-    if (pd.ins[i].op == gxp::VM_LOAD_DEC || pd.ins[i].op == gxp::VM_LOAD_I64)
-      pd.ins[i].c = -1;
+  // the projection kernel loads directly, in program order (no fetch
+  // pipeline, no reorder)
+  if (finishVmProgram(ex, B, 0) < 0) return GX_ERR_INVALID;
   // OUTPUT schema for emission
   ex->desc.table.nCols = (int)ex->projOutTypes.size();
   for (size_t c = 0; c < ex->projOutTypes.size(); c++)
@@ -2342,32 +2109,22 @@ static int32_t compileFused(gx_exec* ex) {
     }
   }
 
-  // consumer counts over the expression DAG (register recycling: a
-  // subexpression's register frees after its last consumer; roots — the
-  // projection outputs the aggregates read — are pinned by not being
-  // counted here)
-  ex->exprUse.clear();
-  ex->vmFreeRegs.clear();
+  // the expression compiler for this attempt (an earlier failed attempt's
+  // state goes with it): full opcode set, registers recycled below the
+  // projection outputs the aggregates read
+  ex->vm = ExprBuilder{};
+  ex->vm.bind(ex->desc, &src->colTypes, &src->colFracs, 0, gxp::kVmOpsFull,
+              gxp::kMaxVmRegs);
+  ex->vm.bindLikePats(ex->desc);
   {
     std::vector<int> roots;
     if (proj) {
-      for (int pe : proj->exprs) roots.push_back(pe);
+      roots = proj->exprs;
     } else {
       for (int a : agg->aggArgs)
         if (a >= 0) roots.push_back(a);
     }
-    std::set<int> visited;
-    std::function<void(int)> cnt = [&](int id) {
-      for (int a : plan.exprs[id].args) {
-        ex->exprUse[a]++;
-        if (visited.insert(a).second) cnt(a);
-      }
-    };
-    for (int r : roots) cnt(r);
-    // a root may also appear as a subexpression (e.g. a projected value the
-    // cast of which is also projected): roots are pinned outputs, never
-    // released
-    for (int r : roots) ex->exprUse.erase(r);
+    ex->vm.countConsumers(plan, roots);
   }
 
   // projection exprs -> VM registers (group-col projections stay colrefs)
@@ -2384,7 +2141,7 @@ static int32_t compileFused(gx_exec* ex) {
         continue;
       }
       int sc = 0;
-      int reg = compileExpr(ex, pe, &sc);
+      int reg = vmCompile(ex, ex->vm, pe, &sc);
       if (reg < 0) return GX_ERR_INVALID;
       projSrcCol.push_back(e.kind == EK_COLREF ? e.colIdx : -1);
       ex->projRegs.push_back({reg, sc});
@@ -2435,7 +2192,7 @@ static int32_t compileFused(gx_exec* ex) {
       }
       forceWideKeys = true;
       int sc = 0;
-      int reg = compileExpr(ex, proj->exprs[e.colIdx], &sc);
+      int reg = vmCompile(ex, ex->vm, proj->exprs[e.colIdx], &sc);
       if (reg < 0) {
         if (ex->err.empty()) ex->err = "group key compile failed";
         return GX_ERR_INVALID;
@@ -2469,7 +2226,7 @@ static int32_t compileFused(gx_exec* ex) {
       // loaded through the VM (canonical units at the column's static scale;
       // load registers are never recycled, so the register is stable)
       int srcExpr = proj ? proj->exprs[e.colIdx] : ge;
-      int reg = compileExpr(ex, srcExpr, &sc);
+      int reg = vmCompile(ex, ex->vm, srcExpr, &sc);
       if (reg < 0) {
         if (ex->err.empty()) ex->err = "group key compile failed";
         return GX_ERR_INVALID;
@@ -2561,7 +2318,7 @@ static int32_t compileFused(gx_exec* ex) {
         ad.scale = ex->projRegs[e.colIdx].second;
       } else {
         int sc = 0;
-        int reg = compileExpr(ex, argE, &sc);
+        int reg = vmCompile(ex, ex->vm, argE, &sc);
         if (reg < 0) return GX_ERR_INVALID;
         ad.srcReg = reg;
         ad.scale = sc;
@@ -2622,66 +2379,28 @@ static int32_t compileFused(gx_exec* ex) {
     ex->desc.accMap[a] = found;
   }
 
-  // assign raw-fetch slots to VM load ops, then move loads to the front of
-  // the instruction stream (each dst is written once, loads have no deps —
-  // the kernel issues [0, nLoadIns) as the batched fetch-consume pipeline)
+  // move loads to the front of the instruction stream (the kernel issues
+  // [0, nLoadIns) as the batched fetch-consume pipeline), then assign their
+  // raw-fetch slots in stream order
   {
     gxp::FusedQueryDesc& d = ex->desc;
-    std::vector<gxp::VmIns> loads, rest;
-    for (int i = 0; i < d.nIns; i++) {
-      gxp::VmIns ins = d.ins[i];
-      if (ins.op == gxp::VM_LOAD_DEC) {
-        ins.c = fetchSlot(ex, gxp::FETCH_DEC16, ins.a);
-        if (ins.c < 0) { ex->err = "fetch plan full"; return GX_ERR_INVALID; }
-        loads.push_back(ins);
-      } else if (ins.op == gxp::VM_LOAD_I64) {
-        ins.c = fetchSlot(ex, gxp::FETCH_8B, ins.a);
-        if (ins.c < 0) { ex->err = "fetch plan full"; return GX_ERR_INVALID; }
-        loads.push_back(ins);
-      } else if (ins.op == gxp::VM_STRLEN) {
-        ins.c = fetchSlot(ex, gxp::FETCH_OFFSETS, ins.a);
-        if (ins.c < 0) { ex->err = "fetch plan full"; return GX_ERR_INVALID; }
-        loads.push_back(ins);
-      } else {
-        rest.push_back(ins);
-      }
+    d.nLoadIns =
+        finishVmProgram(ex, ex->vm, kVmLoadOps | 1u << gxp::VM_STRLEN);
+    if (d.nLoadIns < 0) return GX_ERR_INVALID;
+    for (int i = 0; i < d.nLoadIns; i++) {
+      gxp::VmIns& ins = d.ins[i];
+      ins.c = fetchSlot(ex,
+                        ins.op == gxp::VM_LOAD_DEC   ? gxp::FETCH_DEC16
+                        : ins.op == gxp::VM_LOAD_I64 ? gxp::FETCH_8B
+                                                     : gxp::FETCH_OFFSETS,
+                        ins.a);
+      if (ins.c < 0) { ex->err = "fetch plan full"; return GX_ERR_INVALID; }
     }
-    d.nLoadIns = (int)loads.size();
-    d.nVmRegs = ex->vmNextReg;  // physical register budget for kernel dispatch
-    int k = 0;
-    for (auto& ins : loads) d.ins[k++] = ins;
-    for (auto& ins : rest) d.ins[k++] = ins;
-    // precompute per-instruction power-of-ten constants
-    static const int64_t p10h[19] = {1, 10, 100, 1000, 10000, 100000, 1000000,
-                                     10000000, 100000000, 1000000000,
-                                     10000000000LL, 100000000000LL,
-                                     1000000000000LL, 10000000000000LL,
-                                     100000000000000LL, 1000000000000000LL,
-                                     10000000000000000LL, 100000000000000000LL,
-                                     1000000000000000000LL};
-    static const uint64_t magich[10] = {
-        4611686018427387904ULL, 461168601842738791ULL, 46116860184273880ULL,
-        4611686018427388ULL,    461168601842739ULL,    46116860184274ULL,
-        4611686018428ULL,       461168601843ULL,       46116860185ULL,
-        4611686019ULL};
+    d.nVmRegs = ex->vm.nextReg;  // physical register budget for kernel dispatch
     if (getenv("GX_DEBUG"))
       for (int i = 0; i < d.nIns; i++)
         fprintf(stderr, "[gx] ins[%d] op=%d dst=%d a=%d b=%d c=%d\n", i,
                 d.ins[i].op, d.ins[i].dst, d.ins[i].a, d.ins[i].b, d.ins[i].c);
-    for (int i = 0; i < d.nIns; i++) {
-      d.insP10[i] = 1;
-      d.insMagic[i] = 0;
-      if (d.ins[i].op == gxp::VM_LOAD_DEC) {
-        int f = d.ins[i].b;
-        d.insP10[i] = p10h[f];
-        d.insMagic[i] = magich[9 - f];
-      } else if (d.ins[i].op == gxp::VM_SCALE_UP) {
-        d.insP10[i] = p10h[d.ins[i].b];
-      } else if (d.ins[i].op == gxp::VM_ROUND_SCALE) {
-        int sh = d.ins[i].b - d.ins[i].c;
-        d.insP10[i] = p10h[sh >= 0 ? sh : -sh];
-      }
-    }
     // pick the fetch-pipeline depth: keep raw state within the VGPR budget
     // (~16 bytes per slot per row)
     if (d.nFetch <= 4) d.rbatch = 4;
@@ -3140,7 +2859,8 @@ static int32_t finalizeFusedBind(gx_exec* ex) {
     // opt-in until the pipelining wins back the staging overhead.
     bool ok = tab.nRows >= 256 && getenv("GX_GLDS") &&
               !d.gkey.wideMode &&   // wide keys use the plain kernel
-              ex->vmNextReg <= 12;  // the staged kernel's VmState is 12-reg
+              // the staged kernel's VmState is 12-reg
+              ex->vm.nextReg <= kVmRegsNarrowState;
     for (int s = 0; s < d.nAccSlots && ok; s++)
       ok = d.accKind[s] == 0;  // staged accumulate is sum-only
     // the staged VM runs the core opcode set: no division, rounding or strings
@@ -3468,10 +3188,10 @@ out:
 }
 
 static int32_t runFused(gx_exec* ex) {
-  if (ex->vmHasDiv && !getenv("GX_DIV_NARROW"))
+  if (ex->vm.hasDiv && !getenv("GX_DIV_NARROW"))
     ex->desc.wide = 1;  // DIV quotients rarely fit int64
-  ex->desc.hasDiv = ex->vmHasDiv ? 1 : 0;
-  ex->desc.nVmRegs = ex->vmNextReg;
+  ex->desc.hasDiv = ex->vm.hasDiv ? 1 : 0;
+  ex->desc.nVmRegs = ex->vm.nextReg;
   if (getenv("GX_FORCE_WIDE")) ex->desc.wide = 1;
   // out-of-core aggregation: a generator source above the HBM budget
   // streams in row-range slices instead of materializing whole
@@ -5397,7 +5117,6 @@ static int32_t runProject(gx_exec* ex) {
     if (!ex->devPd) { ex->err = "hipMalloc failed"; return GX_ERR_INTERNAL; }
   }
   pd.errorFlag = ex->devErr;
-  if (ex->vmHasDiv) pd.wide = 1;
   int64_t n = pd.table.nRows;
   // computed-output buffers
   std::vector<uint8_t*> bitmaps(pd.nOut, nullptr);
@@ -6309,6 +6028,40 @@ static int32_t emitResultRows(gx_exec* ex, gx_chunk* out, int32_t* rows_out) {
 
 // ---------------- C ABI ----------------
 
+// text form of one VM program (gx_debug_vm_program)
+template <class Desc>
+static void dumpVmProgram(std::string& s, const char* site, const Desc& d,
+                          int nLoadIns, int nRegs, const gxp::FetchDesc* fetch,
+                          int nFetch, int nLikePats) {
+  // only the fused descriptor stores its register count
+  if (nRegs < 0)
+    for (int i = 0; i < d.nIns; i++) nRegs = std::max(nRegs, d.ins[i].dst + 1);
+  char buf[256];
+  snprintf(buf, sizeof buf, "site %s nIns=%d nLoadIns=%d nVmRegs=%d wide=%d\n",
+           site, d.nIns, nLoadIns, nRegs, d.wide);
+  s += buf;
+  for (int i = 0; i < d.nIns; i++) {
+    const gxp::VmIns& in = d.ins[i];
+    snprintf(buf, sizeof buf,
+             "ins[%d] op=%d dst=%d a=%d b=%d c=%d p10=%lld magic=%llu\n", i,
+             in.op, in.dst, in.a, in.b, in.c, (long long)d.insP10[i],
+             (unsigned long long)d.insMagic[i]);
+    s += buf;
+  }
+  for (int i = 0; i < d.nConsts; i++) {
+    snprintf(buf, sizeof buf, "const[%d] lo=%lld hi=%lld\n", i,
+             (long long)d.constLo[i], (long long)d.constHi[i]);
+    s += buf;
+  }
+  for (int i = 0; i < nFetch; i++) {
+    snprintf(buf, sizeof buf, "fetch[%d] kind=%d col=%d\n", i, fetch[i].kind,
+             fetch[i].col);
+    s += buf;
+  }
+  snprintf(buf, sizeof buf, "likePats=%d\n", nLikePats);
+  s += buf;
+}
+
 extern "C" {
 
 gx_pb* gx_pb_new(void) { return new gx_pb(); }
@@ -6602,10 +6355,6 @@ gx_exec* gx_build(gx_pb* pb, int32_t root, int32_t device) {
         ex->postSortKeys.clear();
         ex->desc = gxp::FusedQueryDesc{};
         ex->projRegs.clear();
-        ex->vmNextReg = 0;
-        ex->exprRegCache.clear();
-        ex->exprUse.clear();
-        ex->vmFreeRegs.clear();
         rc = compileJoinAgg(ex);
         if (rc != GX_OK && ex->jaLikeRejected) {
           ex->postSortKeys.clear();
@@ -6615,10 +6364,6 @@ gx_exec* gx_build(gx_pb* pb, int32_t root, int32_t device) {
           ex->err.clear();
           ex->desc = gxp::FusedQueryDesc{};
           ex->projRegs.clear();
-          ex->vmNextReg = 0;
-          ex->exprRegCache.clear();
-          ex->exprUse.clear();
-          ex->vmFreeRegs.clear();
           ex->postSort = true;
           ex->postSortKeys = savedKeys;
           ex->postLimit = rn.limit;
@@ -6999,6 +6744,30 @@ const char* gx_debug_jit_source(gx_exec* ex) {
   static std::string s;
   if (!ex) return "";
   s = gxjit::generateSource(ex->desc);
+  return s.c_str();
+}
+
+// debug: a text dump of the VM program the plan compiled to, at whichever of
+// the three sites took it (works after gx_build without a GPU; pinned by
+// tests/test_vm_programs.py; not part of the stable ABI)
+const char* gx_debug_vm_program(gx_exec* ex) {
+  static std::string s;
+  s.clear();
+  if (!ex) return "";
+  if (ex->isJoinAgg) {
+    int nLoads = 0;  // the probe kernel does not store it: leading loads
+    while (nLoads < ex->ja.nIns && (ex->ja.ins[nLoads].op == gxp::VM_LOAD_DEC ||
+                                    ex->ja.ins[nLoads].op == gxp::VM_LOAD_I64))
+      nLoads++;
+    dumpVmProgram(s, "probe", ex->ja, nLoads, -1, ex->ja.fetch, ex->ja.nFetch, 0);
+  } else if (ex->isProject) {
+    dumpVmProgram(s, "projection", ex->pd, 0, -1, nullptr, 0, ex->pd.nLikePats);
+  } else if (ex->isFused) {
+    dumpVmProgram(s, "fused", ex->desc, ex->desc.nLoadIns, ex->desc.nVmRegs,
+                  ex->desc.fetch, ex->desc.nFetch, ex->desc.nLikePats);
+  } else {
+    s = "site none\nerror: " + ex->err + "\n";
+  }
   return s.c_str();
 }
 

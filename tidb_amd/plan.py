@@ -380,7 +380,25 @@ def q3_merge_plan(lib, limit=10):
     return b, (cust, orders, li), topn, out_types, out_fracs
 
 
-def q3_plan(lib, limit=10):
+def round_revenue(b, rev, price, disc):
+    """q3_plan wrapper: ROUND(price * (1 - disc), 2), summed at frac 2 -- a
+    value expression outside the join-aggregate probe's opcode set."""
+    from tests.gxlib import GX_F_ROUND
+    return b.call(GX_F_ROUND, GX_TYPE_DECIMAL, 2, rev, b.const_i64(2)), 2
+
+
+def if_revenue(b, rev, price, disc):
+    """q3_plan wrapper: IF(disc > 0.05, price * (1 - disc), price) at frac 4
+    -- VM_CMP, VM_IF and a scale-up, all inside the probe's opcode set."""
+    from tests.gxlib import GX_F_GT, GX_F_IF, dec
+    cut = b.const_dec(bytes(dec(b.lib, "0.05")[0]))
+    big = b.call(GX_F_GT, GX_TYPE_I64, 0, disc, cut)
+    return b.call(GX_F_IF, GX_TYPE_DECIMAL, 4, big, rev, price), 4
+
+
+def q3_plan(lib, limit=10, wrap_revenue=None):
+    """wrap_revenue(b, rev, price, disc) -> (expr, frac) replaces the summed
+    revenue term price * (1 - disc)."""
     from tests.gxlib import GX_F_GT, GX_F_EQ, GX_TPCH_ORDERS, GX_TPCH_CUSTOMER
     b = Builder(lib)
     cust = b.source(CUSTOMER_TYPES)
@@ -423,17 +441,20 @@ def q3_plan(lib, limit=10):
     one = _const_dec_one(lib, b)
     om_d = b.call(GX_F_MINUS, GX_TYPE_DECIMAL, 2, one, disc)
     rev = b.call(GX_F_MUL, GX_TYPE_DECIMAL, 4, price, om_d)
+    fr = 4
+    if wrap_revenue:
+        rev, fr = wrap_revenue(b, rev, price, disc)
     proj = b.projection(j2, [jo_orderkey, jo_odate, jo_prio, rev])
 
     from tests.gxlib import GX_AGG_SUM
     agg = b.hashagg(proj,
                     [b.colref(0, GX_TYPE_I64), b.colref(1, GX_TYPE_TIME),
                      b.colref(2, GX_TYPE_I64)],
-                    [(GX_AGG_SUM, b.colref(3, GX_TYPE_DECIMAL, 4), 4)])
-    # agg out: orderkey, orderdate, shippriority, revenue(dec s4)
-    topn = b.topn(agg, [b.colref(3, GX_TYPE_DECIMAL, 4),
+                    [(GX_AGG_SUM, b.colref(3, GX_TYPE_DECIMAL, fr), fr)])
+    # agg out: orderkey, orderdate, shippriority, revenue(dec at fr)
+    topn = b.topn(agg, [b.colref(3, GX_TYPE_DECIMAL, fr),
                         b.colref(1, GX_TYPE_TIME)],
                   [1, 0], limit)
     out_types = [GX_TYPE_I64, GX_TYPE_TIME, GX_TYPE_I64, GX_TYPE_DECIMAL]
-    out_fracs = [0, 0, 0, 4]
+    out_fracs = [0, 0, 0, fr]
     return b, (cust, orders, li), topn, out_types, out_fracs
