@@ -55,7 +55,11 @@ enum {
   GX_TYPE_STRING = 4   /* var-len (char/varchar), offsets + bytes */
 };
 
-/* ---- chunk ---- */
+/* ---- chunk ----
+ * The engine never interprets the bytes under a NULL of a fixed-width column,
+ * and promises nothing about the bytes under a NULL it emits. (The
+ * reference's Column.AppendNull leaves the previously appended value there;
+ * bound chunks are uploaded as they are, bytes under NULLs included.) */
 typedef struct gx_col {
   void*    data;        /* fixed: elem data; varlen: byte payload */
   uint8_t* null_bitmap; /* ceil(length/8) bytes; LSB-first; 1 = NOT NULL; may be NULL => all not-null */

@@ -282,6 +282,16 @@ def test_fuzz_join_types_model(seed):
         assert got == model(jt), f"join_type {jt}"
 
 
+def null_order_key(vals, desc):
+    """sortexec order as a Python sort key: NULL < any value, and a
+    descending key reverses that (NULLs last). vals are numbers or None."""
+    out = []
+    for v, d in zip(vals, desc):
+        rank = (0 if v is None else 1, 0 if v is None else v)
+        out.append((-rank[0], -rank[1]) if d else rank)
+    return tuple(out)
+
+
 @pytest.mark.parametrize("seed", [13, 61])
 def test_fuzz_sort_nullable_multikey(seed):
     """TopN over 2 nullable keys with random asc/desc vs Python's sort
@@ -310,13 +320,7 @@ def test_fuzz_sort_nullable_multikey(seed):
     ex.free()
     b.free()
 
-    def keyf(r):
-        out = []
-        for v, d in zip(r[:2], desc):
-            # NULL < any value; desc reverses
-            rank = (0 if v is None else 1, 0 if v is None else v)
-            out.append((-rank[0], -rank[1]) if d else rank)
-        return tuple(out)
+    keyf = lambda r: null_order_key(r[:2], desc)
 
     want_keys = [keyf(r) for r in sorted(rows, key=keyf)][:200]
     assert [keyf(r) for r in got] == want_keys

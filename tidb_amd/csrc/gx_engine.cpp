@@ -3866,6 +3866,27 @@ static int32_t runJoinAgg(gx_exec* ex) {
     if (rc) return rc;
     rc = materializeTable(ex, ex->jaSrcOrd, &ja.build1);
     if (rc) return rc;
+    // the group slots carry payload values without a NULL flag: a NULL
+    // payload would come back as whatever bytes lie under it. A comparison
+    // conjunct on the column rejects its NULL rows before they reach a slot
+    // (evalSimplePred; these filters are plain conjunctions); IS NULL keeps
+    // them.
+    auto nullsFiltered = [&](int col) {
+      auto covers = [&](const gxp::PredDesc& p) {
+        return p.col == col &&
+               !(p.kind == gxp::PRED_IS_NULL && p.cmp == 4 /*GX_F_EQ*/);
+      };
+      if (ja.nPred1 > 0 && covers(ja.pred1)) return true;
+      for (int i = 0; i < ja.nPred1x; i++)
+        if (covers(ja.pred1x[i])) return true;
+      return false;
+    };
+    for (int pc : {ja.payloadCol0, ja.payloadCol1})
+      if (pc >= 0 && ja.build1.cols[pc].hasNulls && !nullsFiltered(pc)) {
+        ex->err = "nullable build payload column unsupported in the "
+                  "join-aggregate pipeline";
+        return GX_ERR_INVALID;
+      }
     rc = materializeTable(ex, ex->jaSrcLi, &ja.probe);
     if (rc) return rc;
     ex->devErr = (uint32_t*)devAllocP(ex, 4);
@@ -5541,6 +5562,13 @@ static int32_t runDeviceSort(gx_exec* ex) {
     if (diff != 0) {
       int beginBit = __builtin_ctzll(diff);
       int endBit = 64 - __builtin_clzll(diff);
+      // rocPRIM's merge-sort path (1024 < n <= its merge limit) compares
+      // keys under a mask built as (1 << end_bit) - 1, which shifts a
+      // 64-bit one by 64 when end_bit is 64 and begin_bit is not 0: the
+      // mask degenerates and the rows come out ordered by their low bits.
+      // With begin_bit 0 it takes the unmasked compare. (Keys that reach
+      // bit 63 and share their low bits: even int64 of both signs.)
+      if (endBit == 64) beginBit = 0;
       size_t tb = tmpBytes;
       if (gxp::gxSortPairs(keyA, keyB, idxA, idxB, n, tmp, &tb, beginBit,
                            endBit, ex->stream)) {

@@ -1855,7 +1855,13 @@ __global__ void sortComposeKeysKernel(DevTable tab, SortKeyCompose k,
        i += (int64_t)gridDim.x * blockDim.x) {
     int64_t row = idx[i];
     uint64_t key;
-    if (k.kind == 0) {  // int64: flip sign bit
+    if (colIsNull(c, row)) {
+      // the bytes under a NULL are not data (AppendNull leaves the previous
+      // value there): every NULL composes the key of a zero value, so the
+      // stable value pass keeps NULL rows in inner-key order and no error
+      // flag can come from them; the null-bit pass then places them
+      key = (k.kind == 1 || k.kind == 2) ? 0 : 0x8000000000000000ULL;
+    } else if (k.kind == 0) {  // int64: flip sign bit
       key = gptr<uint64_t>(c.data)[row] ^ 0x8000000000000000ULL;
     } else if (k.kind == 1) {  // packed CoreTime: masked compare order
       key = gptr<uint64_t>(c.data)[row] & ~0xFULL;
