@@ -318,6 +318,16 @@ int64_t gx_last_sel_count(gx_exec* ex);
  * 0 while every decimal still reads the 40-byte form). */
 const char* gx_debug_jit_source(gx_exec* ex);
 int32_t gx_debug_dec_units_cols(gx_exec* ex);
+/* product engine only, debug: the accumulation tier that answered the last
+ * fused pass -- 0 lane-replicated LDS accumulators (generated kernels), 1 the
+ * single 64-slot LDS table, 2 global-direct; -1 before any pass. And the
+ * number of group slots of the plan's replicated LDS table (0 = none). */
+int32_t gx_debug_lds_tier(gx_exec* ex);
+int32_t gx_debug_lds_repl_slots(gx_exec* ex);
+/* product engine only, debug: 1 when the last fused decode read its groups
+ * from the compact result block (one small copy per open), 0 when it took
+ * the full-table download (more than 256 groups, or wide group keys). */
+int32_t gx_debug_result_compact(gx_exec* ex);
 /* product engine only, debug (not part of the stable ABI): a text dump of the
  * expression-VM program the plan compiled to -- site (fused / probe /
  * projection), instruction stream with its precomputed constants, constants,

@@ -321,6 +321,69 @@ struct FusedQueryDesc {
   int32_t nLikePats = 0;
 };
 
+// ---- compact result download ----
+// After the fused launch(es) compactGroupsKernel appends every occupied
+// bank-0 slot (banks 1+ folded in when the noLds pass wrote them) to this
+// block, so one small copy brings back flag, selected-row count and the
+// groups. The header doubles as the pass's error flag / selected-row
+// counter (FusedQueryDesc::errorFlag / selCount point into it) and
+// nOccupied is the kernel's append cursor: it counts every occupied slot,
+// also those beyond kResultCap, which tells the host to fall back to the
+// full-table download.
+constexpr int kResultCap = 256;
+struct FusedResultHdr {
+  uint32_t errorFlag;
+  uint32_t nOccupied;
+  uint64_t selCount;
+};
+struct FusedResultBlock {
+  FusedResultHdr hdr;
+  GroupSlot slots[kResultCap];
+};
+
+#if defined(__HIP__)
+#define GX_HD __host__ __device__
+#else
+#define GX_HD
+#endif
+
+// fold one accumulator bank's slot into the bank-0 slot (all supported states
+// merge: int128 sums and counts add, biased min/max takes the maximum, f64
+// bits add as doubles). Shared by compactGroupsKernel and the host decode of
+// the full-table download so both fold in the same order with the same ops.
+GX_HD inline void foldGroupSlot(GroupSlot& dst, const GroupSlot& b,
+                                int nAccSlots, const int32_t* accKind,
+                                int nCnt) {
+  for (int s = 0; s < nAccSlots; s++) {
+    if (accKind[s] == 3) {
+      double x, y;
+      __builtin_memcpy(&x, &dst.accLo[s], 8);
+      __builtin_memcpy(&y, &b.accLo[s], 8);
+      x += y;
+      __builtin_memcpy(&dst.accLo[s], &x, 8);
+    } else if (accKind[s] != 0) {
+      if (b.accLo[s] > dst.accLo[s]) dst.accLo[s] = b.accLo[s];
+    } else {
+      uint64_t lo = dst.accLo[s] + b.accLo[s];
+      uint64_t carry = lo < dst.accLo[s] ? 1 : 0;
+      dst.accLo[s] = lo;
+      dst.accHi[s] =
+          (int64_t)((uint64_t)dst.accHi[s] + (uint64_t)b.accHi[s] + carry);
+    }
+  }
+  for (int a = 0; a < nCnt; a++) dst.cnt[a] += b.cnt[a];
+}
+
+// occupied slots of a downloaded result block, in arrival order. false =>
+// the block overflowed (more than kResultCap groups): take the full table.
+template <typename Vec>
+inline bool collectCompactGroups(const FusedResultBlock& blk, Vec* occ) {
+  if (blk.hdr.nOccupied > (uint32_t)kResultCap) return false;
+  for (uint32_t i = 0; i < blk.hdr.nOccupied; i++)
+    occ->push_back(&blk.slots[i]);
+  return true;
+}
+
 // ---- join-aggregate pipeline (TPC-H Q3 class) ----
 // customer(filter) -> key set; orders(filter) x set -> slot table keyed by
 // orderkey carrying <=2 payload cols + one int128 accumulator; lineitem
@@ -650,6 +713,10 @@ int gxFusedGrid(int64_t rows);
 int gxBuildDecUnits(const DevCol& col, int64_t nRows, int declaredFrac,
                     int64_t* out, uint32_t* flag, void* stream);
 int gxLaunchInitTable(GroupSlot* table, int64_t nSlots, void* stream);
+// append the occupied slots of the pass's global table to `out` (whose header
+// is the pass's flag/count block); usedBanks > 1 folds the noLds banks
+int gxLaunchCompactGroups(const FusedQueryDesc* devDesc, int globalGroupsLog2,
+                          int usedBanks, FusedResultBlock* out, void* stream);
 int gxDumpDesc(const FusedQueryDesc* devDesc, void* stream);
 
 // ---- device full sort (sortexec/sort.go analog): LSD stable radix passes

@@ -18,6 +18,9 @@ constexpr uint32_t kErrScale = 4u;
 constexpr uint32_t kErrOverflow = 8u;
 constexpr uint32_t kErrLdsFull = 16u;
 constexpr uint32_t kErrGlobalFull = 32u;
+// a block met more keys than the lane-replicated LDS table of a generated
+// kernel holds: the engine reruns with the single-copy layout; not an error
+constexpr uint32_t kErrLdsSmall = 64u;
 constexpr uint32_t kErrRetryWide = 256u;  // narrow VM overflowed; not an error
 
 __host__ __device__ inline uint64_t splitmix64(uint64_t x) {
@@ -791,6 +794,36 @@ __device__ inline void lds3AccumAcc(Lds3GroupSlot* slot, int s, Int128 v) {
       __hip_atomic_fetch_add((Lds3U64*)&slot->accHi[s], (uint64_t)hiAdd,
                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   }
+}
+
+// plain-word variants for the lane-replicated layout of the generated
+// kernels (the caller addresses its own copy of each word)
+__device__ inline void lds3WordAddAcc(Lds3U64* lo, Lds3U64* hi, Int128 v) {
+  if (v.lo != 0 || v.hi != 0) {
+    uint64_t old = __hip_atomic_fetch_add(lo, (uint64_t)v.lo, __ATOMIC_RELAXED,
+                                          __HIP_MEMORY_SCOPE_WORKGROUP);
+    uint64_t carry = (old + v.lo) < old ? 1 : 0;
+    int64_t hiAdd = v.hi + (int64_t)carry;
+    if (hiAdd != 0)
+      __hip_atomic_fetch_add(hi, (uint64_t)hiAdd, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+}
+
+__device__ inline void lds3WordMax(Lds3U64* w, uint64_t enc) {
+  __hip_atomic_fetch_max(w, enc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+__device__ inline void lds3WordAdd(Lds3U64* w, uint64_t dc) {
+  __hip_atomic_fetch_add(w, dc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+__device__ inline uint64_t lds3WordCas(Lds3U64* w, uint64_t expect,
+                                       uint64_t val) {
+  __hip_atomic_compare_exchange_strong(w, &expect, val, __ATOMIC_RELAXED,
+                                       __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_WORKGROUP);
+  return expect;
 }
 
 typedef __attribute__((address_space(3))) double Lds3F64;

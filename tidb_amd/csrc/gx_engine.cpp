@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <map>
 #include <functional>
@@ -316,6 +317,12 @@ struct gx_exec {
   // interpreted fusedAggKernel
   const gxjit::JitProg* jitProg = nullptr;
   bool jitTried = false;
+  // the same plan with lane-replicated LDS accumulators (accumulation tier
+  // 0); ldsNoRepl = a block outgrew its small key table, sticky like noLds
+  const gxjit::JitProg* jitProgRepl = nullptr;
+  bool jitReplTried = false;
+  bool ldsNoRepl = false;
+  int lastLdsTier = -1;  // tier of the last fused pass (gx_debug_lds_tier)
   const gxjit::JitProg* jaJitProg = nullptr;
   bool jaJitTried = false;
   const gxjit::JaBuildProg* jaBuildProg = nullptr;
@@ -334,6 +341,17 @@ struct gx_exec {
   gxp::FusedQueryDesc* devDesc = nullptr;
   uint32_t* devErr = nullptr;
   uint64_t* devSel = nullptr;
+  // fused pass result block (devErr/devSel point into its header) and the
+  // pinned host copy one hipMemcpyAsync per open lands in; resultCompact =
+  // the last pass ran compactGroupsKernel, so hostResult holds the groups
+  gxp::FusedResultBlock* devResult = nullptr;
+  gxp::FusedResultBlock* hostResult = nullptr;
+  bool resultCompact = false;
+  bool lastDecodeCompact = false;  // gx_debug_result_compact
+  // kernel-time events, created once per executor
+  hipEvent_t evK0 = nullptr, evK1 = nullptr;
+  // host shadow of the descriptor as last uploaded to devDesc
+  std::vector<uint8_t> descShadow;
   hipStream_t stream = nullptr;
   // results
   bool ranQuery = false;
@@ -355,6 +373,33 @@ struct gx_exec {
   int64_t spillRemaining = -1;  // limit countdown (-1 = unlimited)
   uint64_t lastSelCount = 0;
   double lastKernelMs = 0;
+  // GX_DEBUG host-side split of one fused open: microseconds per segment
+  // (upload, launch, sync + result block copy, full-table download when the
+  // compact block does not answer, decode)
+  struct HostSplit {
+    bool on = false;
+    std::chrono::steady_clock::time_point last;
+    double us[7] = {0, 0, 0, 0, 0, 0, 0};
+    void begin() {
+      on = getenv("GX_DEBUG") != nullptr;
+      if (!on) return;
+      for (double& u : us) u = 0;
+      last = std::chrono::steady_clock::now();
+    }
+    void lap(int seg) {
+      if (!on) return;
+      auto now = std::chrono::steady_clock::now();
+      us[seg] += std::chrono::duration<double, std::micro>(now - last).count();
+      last = now;
+    }
+    void print() const {
+      if (!on) return;
+      fprintf(stderr,
+              "[gx] host split us: upload=%.1f launch=%.1f sync+d2h=%.1f "
+              "d2h_table=%.1f decode=%.1f\n",
+              us[0], us[1], us[2], us[5], us[6]);
+    }
+  } split;
 
   // post-aggregation host sort (ORDER BY / TopN over the fused agg output)
   bool postSort = false;
@@ -422,6 +467,9 @@ struct gx_exec {
   ~gx_exec() {
     for (void* p : devBufs) hipFree(p);
     for (void* p : persistBufs) hipFree(p);
+    if (hostResult) (void)hipHostFree(hostResult);
+    if (evK0) (void)hipEventDestroy(evK0);
+    if (evK1) (void)hipEventDestroy(evK1);
   }
 };
 
@@ -2839,13 +2887,23 @@ static int32_t finalizeFusedBind(gx_exec* ex) {
   ex->devTable = (gxp::GroupSlot*)devAllocP(
       ex, (sizeof(gxp::GroupSlot) << ex->desc.globalGroupsLog2) *
               ex->desc.accBanks);
-  ex->devErr = (uint32_t*)devAllocP(ex, 4);
-  ex->devSel = (uint64_t*)devAllocP(ex, 8);
+  ex->devResult =
+      (gxp::FusedResultBlock*)devAllocP(ex, sizeof(gxp::FusedResultBlock));
   ex->devDesc = (gxp::FusedQueryDesc*)devAllocP(ex, sizeof(gxp::FusedQueryDesc));
-  if (!ex->devTable || !ex->devErr || !ex->devSel || !ex->devDesc) {
+  if (!ex->devTable || !ex->devResult || !ex->devDesc) {
     ex->err = "hipMalloc failed";
     return GX_ERR_INTERNAL;
   }
+  // the pass's error flag and selected-row counter live in the result
+  // block's header: one memset resets both, one copy brings both back
+  ex->devErr = &ex->devResult->hdr.errorFlag;
+  ex->devSel = &ex->devResult->hdr.selCount;
+  ex->descShadow.clear();
+  if (!ex->hostResult)
+    HIP_OK(ex, hipHostMalloc((void**)&ex->hostResult,
+                             sizeof(gxp::FusedResultBlock), hipHostMallocDefault));
+  if (!ex->evK0) HIP_OK(ex, hipEventCreate(&ex->evK0));
+  if (!ex->evK1) HIP_OK(ex, hipEventCreate(&ex->evK1));
   ex->desc.globalTable = ex->devTable;
   ex->desc.errorFlag = ex->devErr;
   ex->desc.selCount = ex->devSel;
@@ -3032,12 +3090,100 @@ static bool convertPackedKeysToWide(gx_exec* ex) {
   if (!ok) return false;
   g.wideMode = 1;
   ex->desc.useGlds = 0;
-  ex->jitProg = nullptr;  // the packed-key specialization no longer applies
+  // the packed-key specializations no longer apply
+  ex->jitProg = nullptr;
+  ex->jitProgRepl = nullptr;
   return ensureWideKeyStore(ex) == GX_OK;
 }
 
 static int32_t fusedDecodeResults(gx_exec* ex);
 static int64_t hbmBudgetBytes();
+
+// The generated kernel for this pass, or nullptr for the interpreted one.
+// Tier 0 (lane-replicated LDS accumulators) answers until a block meets more
+// keys than its small table holds; each layout compiles on first use, any
+// failure falls through to the next. Also records the pass's tier.
+static const gxjit::JitProg* fusedPickJit(gx_exec* ex, bool mayCompile) {
+  const bool dbg = getenv("GX_DEBUG") != nullptr;
+  auto compile = [&](bool repl) -> const gxjit::JitProg* {
+    bool eligible = !ex->desc.gkey.wideMode;  // wide keys: interpreted kernel
+    for (int k = 0; k < ex->desc.gkey.nCols; k++)
+      eligible &= ex->desc.gkey.kind[k] != 0;
+    if (!eligible) return nullptr;
+    std::string why;
+    const gxjit::JitProg* p = gxjit::compile(ex->desc, repl, &why);
+    if (dbg)
+      fprintf(stderr, "[gx] jit %s%s%s\n", p ? "ok" : "DISABLED: ",
+              p ? "" : why.c_str(), repl ? " (replicated LDS layout)" : "");
+    return p;
+  };
+  const gxjit::JitProg* prog = nullptr;
+  bool repl = false;
+  if (!ex->ldsNoRepl && !ex->desc.noLds && !getenv("GX_NO_LDS_REPL")) {
+    if (!ex->jitReplTried && mayCompile) {
+      ex->jitReplTried = true;
+      ex->jitProgRepl = compile(true);
+    }
+    prog = ex->jitProgRepl;
+    repl = prog != nullptr;
+  }
+  if (!prog) {
+    if (!ex->jitTried && mayCompile) {
+      ex->jitTried = true;
+      ex->jitProg = compile(false);
+    }
+    prog = ex->jitProg;
+  }
+  ex->lastLdsTier = ex->desc.noLds ? 2 : (repl ? 0 : 1);
+  return prog;
+}
+
+// reset the pass's header on the stream: error flag and group cursor always,
+// the selected-row count unless a later streaming slice keeps counting
+static hipError_t fusedResetHeader(gx_exec* ex, bool keepSel) {
+  return hipMemsetAsync(&ex->devResult->hdr, 0,
+                        keepSel ? offsetof(gxp::FusedResultHdr, selCount)
+                                : sizeof(gxp::FusedResultHdr),
+                        ex->stream);
+}
+
+// upload the descriptor only when it differs from the last uploaded copy
+// (a retry that edits the descriptor uploads naturally)
+static hipError_t fusedUploadDesc(gx_exec* ex) {
+  const size_t n = sizeof(ex->desc);
+  if (ex->descShadow.size() == n &&
+      std::memcmp(ex->descShadow.data(), &ex->desc, n) == 0)
+    return hipSuccess;
+  ex->descShadow.resize(n);
+  std::memcpy(ex->descShadow.data(), &ex->desc, n);
+  return hipMemcpyAsync(ex->devDesc, ex->descShadow.data(), n,
+                        hipMemcpyHostToDevice, ex->stream);
+}
+
+// end of a pass: with `groups`, compact the occupied slots into the result
+// block (wide-key plans keep the full-table download: the decode needs their
+// key records), then ONE copy of header (+ records) into the pinned block and
+// ONE sync. Every retry branch reads the flag from that header.
+static int32_t fusedFetchResult(gx_exec* ex, bool groups) {
+  size_t bytes = sizeof(gxp::FusedResultHdr);
+  ex->resultCompact = false;
+  if (groups && !ex->desc.gkey.wideMode) {
+    int lrc = gxp::gxLaunchCompactGroups(
+        ex->devDesc, ex->desc.globalGroupsLog2,
+        ex->desc.noLds ? ex->desc.accBanks : 1, ex->devResult, ex->stream);
+    if (lrc != 0) {
+      ex->err = "group compaction launch failed: " +
+                std::string(hipGetErrorString((hipError_t)lrc));
+      return GX_ERR_INTERNAL;
+    }
+    bytes = sizeof(gxp::FusedResultBlock);
+    ex->resultCompact = true;
+  }
+  HIP_OK(ex, hipMemcpyAsync(ex->hostResult, ex->devResult, bytes,
+                            hipMemcpyDeviceToHost, ex->stream));
+  HIP_OK(ex, hipStreamSynchronize(ex->stream));
+  return GX_OK;
+}
 
 // out-of-core aggregation (the agg_spill.go analog, MI355X-shaped): the
 // GROUP STATES stay resident in HBM — bounded by the grown global table —
@@ -3079,38 +3225,25 @@ restart:
     }
     {
       ex->desc.ablate = 0;
-      HIP_OK(ex, hipMemsetAsync(ex->devErr, 0, 4, ex->stream));
-      if (done == 0) HIP_OK(ex, hipMemsetAsync(ex->devSel, 0, 8, ex->stream));
-      HIP_OK(ex, hipMemcpyAsync(ex->devDesc, &ex->desc, sizeof(ex->desc),
-                                hipMemcpyHostToDevice, ex->stream));
+      HIP_OK(ex, fusedResetHeader(ex, done != 0));
+      HIP_OK(ex, fusedUploadDesc(ex));
       if (ex->desc.noLds) ex->desc.useGlds = 0;
-      hipEvent_t ev0, ev1;
-      HIP_OK(ex, hipEventCreate(&ev0));
-      HIP_OK(ex, hipEventCreate(&ev1));
-      HIP_OK(ex, hipEventRecord(ev0, ex->stream));
-      if (!ex->jitTried && !ex->desc.useGlds && !getenv("GX_NO_JIT")) {
-        ex->jitTried = true;
-        bool eligible = !ex->desc.gkey.wideMode;
-        for (int k = 0; k < ex->desc.gkey.nCols; k++)
-          eligible &= ex->desc.gkey.kind[k] != 0;
-        if (eligible) {
-          std::string why;
-          ex->jitProg = gxjit::compile(ex->desc, &why);
-        }
-      }
+      HIP_OK(ex, hipEventRecord(ex->evK0, ex->stream));
+      const gxjit::JitProg* prog =
+          fusedPickJit(ex, !ex->desc.useGlds && !getenv("GX_NO_JIT"));
       int lrc;
-      if (ex->jitProg) {
+      if (prog) {
         lrc = done == 0 ? gxp::gxLaunchInitTable(
                               ex->desc.globalTable,
                               (int64_t)(1 << ex->desc.globalGroupsLog2) *
-                                  ex->desc.accBanks,
+                                  (ex->desc.noLds ? ex->desc.accBanks : 1),
                               ex->stream)
                         : 0;
         if (lrc == 0 && done == 0 && ex->desc.gkey.wideMode &&
             ex->desc.gkey.recCursor)
           lrc = (int)hipMemsetAsync(ex->desc.gkey.recCursor, 0, 8, ex->stream);
         if (lrc == 0)
-          lrc = gxjit::launch(ex->jitProg, ex->desc.wide != 0, ex->devDesc,
+          lrc = gxjit::launch(prog, ex->desc.wide != 0, ex->devDesc,
                               gxp::gxFusedGrid(ex->desc.table.nRows),
                               ex->stream);
       } else {
@@ -3123,16 +3256,20 @@ restart:
         rc = GX_ERR_INTERNAL;
         goto out;
       }
-      HIP_OK(ex, hipEventRecord(ev1, ex->stream));
-      HIP_OK(ex, hipStreamSynchronize(ex->stream));
+      HIP_OK(ex, hipEventRecord(ex->evK1, ex->stream));
+      // the last slice also compacts the groups: the table is complete then
+      rc = fusedFetchResult(ex, done + n >= total);
+      if (rc) goto out;
       float ms = 0;
-      hipEventElapsedTime(&ms, ev0, ev1);
+      hipEventElapsedTime(&ms, ex->evK0, ex->evK1);
       ex->lastKernelMs += ms;
-      hipEventDestroy(ev0);
-      hipEventDestroy(ev1);
     }
-    uint32_t errFlag = 0;
-    HIP_OK(ex, hipMemcpy(&errFlag, ex->devErr, 4, hipMemcpyDeviceToHost));
+    uint32_t errFlag = ex->hostResult->hdr.errorFlag;
+    if ((errFlag & 64u) && !ex->ldsNoRepl) {
+      ex->ldsNoRepl = true;
+      freeSince(ex, mark);
+      goto restart;
+    }
     if (errFlag == 256u && !ex->desc.wide) {
       ex->desc.wide = 1;
       freeSince(ex, mark);
@@ -3183,7 +3320,7 @@ out:
   b.tpchRowOffset = saveOff;
   b.tpchTotalRows = saveTot;
   if (rc) return rc;
-  HIP_OK(ex, hipMemcpy(&ex->lastSelCount, ex->devSel, 8, hipMemcpyDeviceToHost));
+  ex->lastSelCount = ex->hostResult->hdr.selCount;
   return fusedDecodeResults(ex);
 }
 
@@ -3216,33 +3353,18 @@ static int32_t runFused(gx_exec* ex) {
   }
   int32_t rc = materializeDevice(ex);
   if (rc) return rc;
+  ex->split.begin();
   ex->desc.ablate = getenv("GX_ABLATE") ? atoi(getenv("GX_ABLATE")) : 0;
-  HIP_OK(ex, hipMemsetAsync(ex->devErr, 0, 4, ex->stream));
-  HIP_OK(ex, hipMemsetAsync(ex->devSel, 0, 8, ex->stream));
-  HIP_OK(ex, hipMemcpyAsync(ex->devDesc, &ex->desc, sizeof(ex->desc),
-                            hipMemcpyHostToDevice, ex->stream));
-  hipEvent_t ev0, ev1;
-  HIP_OK(ex, hipEventCreate(&ev0));
-  HIP_OK(ex, hipEventCreate(&ev1));
-  HIP_OK(ex, hipEventRecord(ev0, ex->stream));
+  HIP_OK(ex, fusedResetHeader(ex, false));
+  HIP_OK(ex, fusedUploadDesc(ex));
+  HIP_OK(ex, hipEventRecord(ex->evK0, ex->stream));
+  ex->split.lap(0);
   if (ex->desc.noLds) ex->desc.useGlds = 0;  // high-NDV retry uses the plain kernel
-  // runtime kernel specialization (gx_jit.cpp): try once per executor, any
-  // failure -> interpreted path. Disabled for the glds variant, timing
-  // ablations and general string group keys.
-  if (!ex->jitTried && !ex->desc.useGlds && ex->desc.ablate == 0 &&
-      !getenv("GX_NO_JIT")) {
-    ex->jitTried = true;
-    bool eligible = !ex->desc.gkey.wideMode;  // wide keys: interpreted kernel
-    for (int k = 0; k < ex->desc.gkey.nCols; k++)
-      eligible &= ex->desc.gkey.kind[k] != 0;
-    if (eligible) {
-      std::string why;
-      ex->jitProg = gxjit::compile(ex->desc, &why);
-      if (getenv("GX_DEBUG"))
-        fprintf(stderr, "[gx] jit %s%s\n", ex->jitProg ? "ok" : "DISABLED: ",
-                ex->jitProg ? "" : why.c_str());
-    }
-  }
+  // runtime kernel specialization (gx_jit.cpp): each layout compiles once
+  // per executor, any failure -> interpreted path. Disabled for the glds
+  // variant, timing ablations and general string group keys.
+  const gxjit::JitProg* prog = fusedPickJit(
+      ex, !ex->desc.useGlds && ex->desc.ablate == 0 && !getenv("GX_NO_JIT"));
   if (getenv("GX_DEBUG_DESC")) {
     fprintf(stderr, "[host] sizeof(desc)=%d aggs_off=%d ins_off=%d\n",
             (int)sizeof(gxp::FusedQueryDesc),
@@ -3251,13 +3373,14 @@ static int32_t runFused(gx_exec* ex) {
     gxp::gxDumpDesc(ex->devDesc, ex->stream);
   }
   int lrc;
-  if (ex->jitProg) {
+  if (prog) {
     lrc = gxp::gxLaunchInitTable(
         ex->desc.globalTable,
-        (int64_t)(1 << ex->desc.globalGroupsLog2) * ex->desc.accBanks,
+        (int64_t)(1 << ex->desc.globalGroupsLog2) *
+            (ex->desc.noLds ? ex->desc.accBanks : 1),
         ex->stream);
     if (lrc == 0)
-      lrc = gxjit::launch(ex->jitProg, ex->desc.wide != 0, ex->devDesc,
+      lrc = gxjit::launch(prog, ex->desc.wide != 0, ex->devDesc,
                           gxp::gxFusedGrid(ex->desc.table.nRows), ex->stream);
   } else {
     lrc = gxp::gxLaunchFusedAgg(ex->desc, ex->devDesc, ex->stream);
@@ -3267,17 +3390,26 @@ static int32_t runFused(gx_exec* ex) {
               std::string(hipGetErrorString((hipError_t)lrc));
     return GX_ERR_INTERNAL;
   }
-  HIP_OK(ex, hipEventRecord(ev1, ex->stream));
-  HIP_OK(ex, hipStreamSynchronize(ex->stream));
+  HIP_OK(ex, hipEventRecord(ex->evK1, ex->stream));
+  ex->split.lap(1);
+  rc = fusedFetchResult(ex, true);
+  if (rc) return rc;
   {
     float ms = 0;
-    hipEventElapsedTime(&ms, ev0, ev1);
+    hipEventElapsedTime(&ms, ex->evK0, ex->evK1);
     ex->lastKernelMs = ms;
-    hipEventDestroy(ev0);
-    hipEventDestroy(ev1);
   }
-  uint32_t errFlag = 0;
-  HIP_OK(ex, hipMemcpy(&errFlag, ex->devErr, 4, hipMemcpyDeviceToHost));
+  ex->split.lap(2);
+  uint32_t errFlag = ex->hostResult->hdr.errorFlag;
+  if ((errFlag & 64u /*kErrLdsSmall*/) && !ex->ldsNoRepl) {
+    // a block met more keys than the replicated LDS table holds: rerun with
+    // the 64-slot single-copy layout (sticky for this executor; the block-
+    // entry flag check made the doomed pass cheap)
+    ex->ldsNoRepl = true;
+    if (getenv("GX_DEBUG"))
+      fprintf(stderr, "[gx] replicated LDS table full -> single-copy retry\n");
+    return runFused(ex);
+  }
   if (errFlag == 256u /*kErrRetryWide only*/ && !ex->desc.wide) {
     // a value overflowed the int64 fast path: rerun with the int128 VM
     // (sticky for this executor)
@@ -3326,14 +3458,15 @@ static int32_t runFused(gx_exec* ex) {
               " (unsupported data shape or overflow)";
     return GX_ERR_INTERNAL;
   }
-  HIP_OK(ex, hipMemcpy(&ex->lastSelCount, ex->devSel, 8, hipMemcpyDeviceToHost));
+  ex->lastSelCount = ex->hostResult->hdr.selCount;
   if (getenv("GX_DEBUG")) {
     fprintf(stderr,
             "[gx] nRows=%lld nPreds=%d nIns=%d nAggs=%d gkeyCols=%d sel=%llu "
-            "kms=%.3f\n",
+            "kms=%.3f lds_tier=%d (0 replicated x%d slots, 1 single, 2 global)\n",
             (long long)ex->desc.table.nRows, ex->desc.nPreds, ex->desc.nIns,
             ex->desc.nAggs, ex->desc.gkey.nCols,
-            (unsigned long long)ex->lastSelCount, ex->lastKernelMs);
+            (unsigned long long)ex->lastSelCount, ex->lastKernelMs,
+            ex->lastLdsTier, gxjit::replSlots(ex->desc));
   }
   return fusedDecodeResults(ex);
 }
@@ -3347,42 +3480,33 @@ static int32_t fusedDecodeResults(gx_exec* ex) {
   // and fold just bank 0 otherwise (a 16x table D2H every step cost the
   // Q1 decode ~28 ms of pure host overhead)
   const int usedBanks = ex->desc.noLds ? ex->desc.accBanks : 1;
-  std::vector<gxp::GroupSlot> table((size_t)nSlots1 * usedBanks);
-  HIP_OK(ex, hipMemcpy(table.data(), ex->devTable,
-                       table.size() * sizeof(gxp::GroupSlot),
-                       hipMemcpyDeviceToHost));
-  // fold the accumulator banks into bank 0 (sums/counts add, biased
-  // min/max takes the extreme, f64 bits add as doubles)
-  for (int bank = 1; bank < usedBanks; bank++) {
-    for (int64_t i = 0; i < nSlots1; i++) {
-      gxp::GroupSlot& dst = table[i];
-      const gxp::GroupSlot& b = table[bank * nSlots1 + i];
-      if (dst.key == gxp::kEmptyKey) continue;
-      for (int s = 0; s < ex->desc.nAccSlots; s++) {
-        if (ex->desc.accKind[s] == 3) {
-          double x, y;
-          std::memcpy(&x, &dst.accLo[s], 8);
-          std::memcpy(&y, &b.accLo[s], 8);
-          x += y;
-          std::memcpy(&dst.accLo[s], &x, 8);
-        } else if (ex->desc.accKind[s] != 0) {
-          if (b.accLo[s] > dst.accLo[s]) dst.accLo[s] = b.accLo[s];
-        } else {
-          __int128 v = (((__int128)dst.accHi[s]) << 64) | dst.accLo[s];
-          v += (((__int128)b.accHi[s]) << 64) | b.accLo[s];
-          dst.accLo[s] = (uint64_t)v;
-          dst.accHi[s] = (int64_t)(v >> 64);
-        }
-      }
-      int nCnt = ex->desc.sharedCnt ? 1 : ex->desc.nAggs;
-      for (int a = 0; a < nCnt; a++) dst.cnt[a] += b.cnt[a];
-    }
-  }
-  table.resize((size_t)nSlots1);
-  // collect occupied slots, deterministic order (by key)
+  // the compact block answers unless it overflowed or the pass skipped it
+  // (wide keys); then the whole table comes down as before
   std::vector<const gxp::GroupSlot*> occ;
-  for (auto& s : table)
-    if (s.key != gxp::kEmptyKey) occ.push_back(&s);
+  const bool compact =
+      ex->resultCompact && gxp::collectCompactGroups(*ex->hostResult, &occ);
+  ex->lastDecodeCompact = compact;
+  std::vector<gxp::GroupSlot> table;
+  if (!compact) {
+    occ.clear();
+    table.resize((size_t)nSlots1 * usedBanks);
+    HIP_OK(ex, hipMemcpy(table.data(), ex->devTable,
+                         table.size() * sizeof(gxp::GroupSlot),
+                         hipMemcpyDeviceToHost));
+    // fold the accumulator banks into bank 0 (gxp::foldGroupSlot, the fold
+    // compactGroupsKernel applies on device)
+    const int nCnt = ex->desc.sharedCnt ? 1 : ex->desc.nAggs;
+    for (int bank = 1; bank < usedBanks; bank++)
+      for (int64_t i = 0; i < nSlots1; i++)
+        if (table[i].key != gxp::kEmptyKey)
+          gxp::foldGroupSlot(table[i], table[bank * nSlots1 + i],
+                             ex->desc.nAccSlots, ex->desc.accKind, nCnt);
+    table.resize((size_t)nSlots1);
+    for (auto& s : table)
+      if (s.key != gxp::kEmptyKey) occ.push_back(&s);
+  }
+  ex->split.lap(5);
+  // occupied slots in deterministic order (by key)
   std::sort(occ.begin(), occ.end(),
             [](const gxp::GroupSlot* a, const gxp::GroupSlot* b) {
               return a->key < b->key;
@@ -3612,6 +3736,8 @@ static int32_t fusedDecodeResults(gx_exec* ex) {
     }
     ex->resultRows.push_back(std::move(row));
   }
+  ex->split.lap(6);
+  ex->split.print();
   if (ex->distinctNKeys >= 0) {
     // fold the deduplicated (keys..., args...) rows back to the user's
     // schema. Inner rows are unique (keys, arg tuple) combinations; a
@@ -6771,7 +6897,8 @@ const char* gx_last_error(gx_exec* ex) {
 const char* gx_debug_jit_source(gx_exec* ex) {
   static std::string s;
   if (!ex) return "";
-  s = gxjit::generateSource(ex->desc);
+  s = gxjit::generateSource(
+      ex->desc, !ex->ldsNoRepl && !ex->desc.noLds && !getenv("GX_NO_LDS_REPL"));
   return s.c_str();
 }
 
@@ -6803,6 +6930,21 @@ const char* gx_debug_vm_program(gx_exec* ex) {
 // table + join-agg probe); 0 when every decimal still reads the 40 B form
 int32_t gx_debug_dec_units_cols(gx_exec* ex) {
   return ex ? ex->decUnitsFused + ex->decUnitsJa : 0;
+}
+
+// debug: accumulation tier of the last fused pass -- 0 lane-replicated LDS
+// accumulators, 1 single 64-slot LDS table, 2 global-direct; -1 before one
+int32_t gx_debug_lds_tier(gx_exec* ex) { return ex ? ex->lastLdsTier : -1; }
+
+// debug: 1 when the last fused decode read its groups from the compact result
+// block, 0 when it took the full-table download
+int32_t gx_debug_result_compact(gx_exec* ex) {
+  return ex && ex->lastDecodeCompact ? 1 : 0;
+}
+
+// debug: group slots of the replicated LDS table for this plan (0 = none)
+int32_t gx_debug_lds_repl_slots(gx_exec* ex) {
+  return ex && ex->isFused ? gxjit::replSlots(ex->desc) : 0;
 }
 
 double gx_last_kernel_ms(gx_exec* ex) { return ex ? ex->lastKernelMs : 0; }

@@ -172,11 +172,63 @@ static void emitVmOp(std::ostringstream& s, const gxp::VmIns& ins, int64_t p10,
     << reg("v", ins.dst) << " = t2; " << reg("n", ins.dst) << " = t3; }\n";
 }
 
-// emit the per-row pipeline with every plan constant baked in
-static void emitRowPipe(std::ostringstream& s, const FusedQueryDesc& d) {
+// Lane-replicated LDS layout of a generated kernel (first accumulation tier):
+// S single keys, and per group W accumulator words in R copies each -- a
+// lane adds into copy threadIdx.x & (R-1), so the lanes of one wave that
+// meet the same group spread over R addresses instead of taking turns on
+// one. Only what the plan uses gets a word: int128 sums two (lo, hi),
+// min/max one, each count one. The copies of one word are contiguous:
+// word w of copy c of slot g is acc[(g * W + w) * R + c].
+struct ReplLayout {
+  int R = 0, S = 0, W = 0;
+  int accWord[gxp::kMaxAggs];
+  int cntWord[gxp::kMaxAggs];
+};
+
+// static LDS of the single-copy layout; the replicated one stays inside it
+// so a block keeps its 8-per-CU occupancy
+static constexpr int kLdsBudgetBytes =
+    (int)sizeof(gxp::GroupSlot) * gxp::kLdsGroups;
+
+static bool planRepl(const FusedQueryDesc& d, ReplLayout* L) {
+  int w = 0;
+  for (int i = 0; i < d.nAccSlots; i++) {
+    L->accWord[i] = w;
+    w += d.accKind[i] == 0 ? 2 : 1;
+  }
+  const int nCnt = d.sharedCnt ? 1 : d.nAggs;
+  for (int a = 0; a < nCnt; a++) L->cntWord[a] = w++;
+  L->W = w;
+  int r = 8;  // copies: 8, 16 or 32 (GX_LDS_REPL_R; default by measurement)
+  if (const char* e = getenv("GX_LDS_REPL_R")) {
+    int v = atoi(e);
+    if (v == 8 || v == 16 || v == 32) r = v;
+  }
+  auto fit = [&](int copies) {  // largest power-of-two slot count, <= 16
+    int sl = 16;
+    while (sl > 0 && sl * (8 + copies * 8 * w) > kLdsBudgetBytes) sl >>= 1;
+    return sl;
+  };
+  while (r > 8 && fit(r) < 8) r >>= 1;
+  L->R = r;
+  L->S = fit(r);
+  return w > 0 && L->S >= 2;
+}
+
+int replSlots(const FusedQueryDesc& d) {
+  ReplLayout L;
+  return planRepl(d, &L) ? L.S : 0;
+}
+
+// emit the per-row pipeline with every plan constant baked in; L selects the
+// lane-replicated LDS layout
+static void emitRowPipe(std::ostringstream& s, const FusedQueryDesc& d,
+                        const ReplLayout* L) {
   s << "template <bool WIDE>\n"
        "__device__ __forceinline__ bool rowPipe(const FusedQueryDesc& d, "
-       "int64_t row, const RawT& raw, Lds3GroupSlot* lds, uint64_t* mySel) {\n"
+       "int64_t row, const RawT& raw, "
+    << (L ? "Lds3U64* lkeys, Lds3U64* lacc" : "Lds3GroupSlot* lds")
+    << ", uint64_t* mySel) {\n"
        "  using T = typename VT<WIDE>::T;\n"
        "  bool ovf = false; (void)ovf;\n";
   // registers are RECYCLED by the plan compiler
@@ -304,48 +356,103 @@ static void emitRowPipe(std::ostringstream& s, const FusedQueryDesc& d) {
   if (d.gkey.nCols == 0) s << "  key = 0;\n";
   s << "  if (key == kEmptyKey) key = kEmptyKey - 1;\n";
   // ---- group probe + accumulate (literal plan; runtime noLds retry) ----
-  s << "  if (!d.noLds) {\n"
-       "    uint32_t slot = (uint32_t)(splitmix64(key) & (kLdsGroups - 1));\n"
-       "    for (int probe = 0;; probe++) {\n"
-       "      if (probe >= kLdsGroups) { atomicOr(d.errorFlag, kErrLdsFull); "
-       "return false; }\n"
-       "      uint64_t cur = lds[slot].key;\n"
-       "      if (cur == key) break;\n"
-       "      if (cur == kEmptyKey) {\n"
-       "        uint64_t prev = lds3CasKey(&lds[slot], kEmptyKey, key);\n"
-       "        if (prev == kEmptyKey || prev == key) break;\n"
-       "      }\n"
-       "      slot = (slot + 1) & (kLdsGroups - 1);\n"
-       "    }\n"
-       "    Lds3GroupSlot* t = &lds[slot];\n";
-  if (d.sharedCnt) s << "    lds3AccumCnt(t, 0, 1);\n";
-  for (int sIdx = 0; sIdx < d.nAccSlots; sIdx++) {
-    if (d.accKind[sIdx] == 0) {
-      s << "    if (!n" << d.accReg[sIdx] << ") lds3AccumAcc(t, " << sIdx
-        << ", VT<WIDE>::toAcc(v" << d.accReg[sIdx] << "));\n";
-    } else {
-      s << "    if (!n" << d.accReg[sIdx] << ") { Int128 mv = "
-           "VT<WIDE>::toAcc(v" << d.accReg[sIdx] << ");\n"
-        << "      bool fits = (mv.hi == 0 && (int64_t)mv.lo >= 0) || "
-           "(mv.hi == -1 && (int64_t)mv.lo < 0);\n"
-        << "      if (WIDE && !fits) { atomicOr(d.errorFlag, kErrOverflow); "
-           "return false; }\n"
-        << "      uint64_t enc = biasI64((int64_t)mv.lo);\n"
-        << "      lds3AccumMax(t, " << sIdx << ", "
-        << (d.accKind[sIdx] == 2 ? "~enc" : "enc") << "); }\n";
+  if (L) {
+    // replicated tier: a block that meets more keys than the small table
+    // holds asks for the single-copy layout (kErrLdsSmall)
+    s << "  if (!d.noLds) {\n"
+         "    uint32_t slot = (uint32_t)(splitmix64(key) & (kReplSlots - 1));\n"
+         // the small constant bound invites full unrolling of a loop that
+         // ends at its first probe: 8 VGPRs for nothing
+         "    _Pragma(\"nounroll\") for (int probe = 0;; probe++) {\n"
+         "      if (probe >= kReplSlots) { atomicOr(d.errorFlag, kErrLdsSmall); "
+         "return false; }\n"
+         "      uint64_t cur = lkeys[slot];\n"
+         "      if (cur == key) break;\n"
+         "      if (cur == kEmptyKey) {\n"
+         "        uint64_t prev = lds3WordCas(&lkeys[slot], kEmptyKey, key);\n"
+         "        if (prev == kEmptyKey || prev == key) break;\n"
+         "      }\n"
+         "      slot = (slot + 1) & (kReplSlots - 1);\n"
+         "    }\n"
+         "    Lds3U64* t = lacc + slot * (kReplWords * kReplCopies);\n";
+    auto word = [&](int w) {
+      return "t + " + std::to_string(w) + " * kReplCopies";
+    };
+    if (d.sharedCnt) s << "    lds3WordAdd(" << word(L->cntWord[0]) << ", 1);\n";
+    for (int sIdx = 0; sIdx < d.nAccSlots; sIdx++) {
+      if (d.accKind[sIdx] == 0) {
+        s << "    if (!n" << d.accReg[sIdx] << ") lds3WordAddAcc("
+          << word(L->accWord[sIdx]) << ", " << word(L->accWord[sIdx] + 1)
+          << ", VT<WIDE>::toAcc(v" << d.accReg[sIdx] << "));\n";
+      } else {
+        s << "    if (!n" << d.accReg[sIdx] << ") { Int128 mv = "
+             "VT<WIDE>::toAcc(v" << d.accReg[sIdx] << ");\n"
+          << "      bool fits = (mv.hi == 0 && (int64_t)mv.lo >= 0) || "
+             "(mv.hi == -1 && (int64_t)mv.lo < 0);\n"
+          << "      if (WIDE && !fits) { atomicOr(d.errorFlag, kErrOverflow); "
+             "return false; }\n"
+          << "      uint64_t enc = biasI64((int64_t)mv.lo);\n"
+          << "      lds3WordMax(" << word(L->accWord[sIdx]) << ", "
+          << (d.accKind[sIdx] == 2 ? "~enc" : "enc") << "); }\n";
+      }
     }
-  }
-  if (!d.sharedCnt) {
-    for (int a = 0; a < d.nAggs; a++) {
-      const gxp::AggDesc& ad = d.aggs[a];
-      if (ad.fr >= 0) continue;
-      if (ad.srcReg >= 0)
-        s << "    if (!n" << ad.srcReg << ") lds3AccumCnt(t, " << a << ", 1);\n";
-      else
-        s << "    lds3AccumCnt(t, " << a << ", 1);\n";
+    if (!d.sharedCnt) {
+      for (int a = 0; a < d.nAggs; a++) {
+        const gxp::AggDesc& ad = d.aggs[a];
+        if (ad.fr >= 0) continue;
+        if (ad.srcReg >= 0)
+          s << "    if (!n" << ad.srcReg << ") lds3WordAdd("
+            << word(L->cntWord[a]) << ", 1);\n";
+        else
+          s << "    lds3WordAdd(" << word(L->cntWord[a]) << ", 1);\n";
+      }
     }
+    s << "    return true;\n  }\n";
+  } else {
+    s << "  if (!d.noLds) {\n"
+         "    uint32_t slot = (uint32_t)(splitmix64(key) & (kLdsGroups - 1));\n"
+         "    for (int probe = 0;; probe++) {\n"
+         "      if (probe >= kLdsGroups) { atomicOr(d.errorFlag, kErrLdsFull); "
+         "return false; }\n"
+         "      uint64_t cur = lds[slot].key;\n"
+         "      if (cur == key) break;\n"
+         "      if (cur == kEmptyKey) {\n"
+         "        uint64_t prev = lds3CasKey(&lds[slot], kEmptyKey, key);\n"
+         "        if (prev == kEmptyKey || prev == key) break;\n"
+         "      }\n"
+         "      slot = (slot + 1) & (kLdsGroups - 1);\n"
+         "    }\n"
+         "    Lds3GroupSlot* t = &lds[slot];\n";
+    if (d.sharedCnt) s << "    lds3AccumCnt(t, 0, 1);\n";
+    for (int sIdx = 0; sIdx < d.nAccSlots; sIdx++) {
+      if (d.accKind[sIdx] == 0) {
+        s << "    if (!n" << d.accReg[sIdx] << ") lds3AccumAcc(t, " << sIdx
+          << ", VT<WIDE>::toAcc(v" << d.accReg[sIdx] << "));\n";
+      } else {
+        s << "    if (!n" << d.accReg[sIdx] << ") { Int128 mv = "
+             "VT<WIDE>::toAcc(v" << d.accReg[sIdx] << ");\n"
+          << "      bool fits = (mv.hi == 0 && (int64_t)mv.lo >= 0) || "
+             "(mv.hi == -1 && (int64_t)mv.lo < 0);\n"
+          << "      if (WIDE && !fits) { atomicOr(d.errorFlag, kErrOverflow); "
+             "return false; }\n"
+          << "      uint64_t enc = biasI64((int64_t)mv.lo);\n"
+          << "      lds3AccumMax(t, " << sIdx << ", "
+          << (d.accKind[sIdx] == 2 ? "~enc" : "enc") << "); }\n";
+      }
+    }
+    if (!d.sharedCnt) {
+      for (int a = 0; a < d.nAggs; a++) {
+        const gxp::AggDesc& ad = d.aggs[a];
+        if (ad.fr >= 0) continue;
+        if (ad.srcReg >= 0)
+          s << "    if (!n" << ad.srcReg << ") lds3AccumCnt(t, " << a
+            << ", 1);\n";
+        else
+          s << "    lds3AccumCnt(t, " << a << ", 1);\n";
+      }
+    }
+    s << "    return true;\n  }\n";
   }
-  s << "    return true;\n  }\n";
   // global-direct path
   s << "  { uint32_t gmask = (1u << d.globalGroupsLog2) - 1;\n"
        "    uint32_t slot = (uint32_t)(splitmix64(key) & gmask);\n"
@@ -433,7 +540,9 @@ static void emitFetch(std::ostringstream& s, const FusedQueryDesc& d) {
   s << "}\n\n";
 }
 
-std::string generateSource(const FusedQueryDesc& d) {
+static std::string genSource(const FusedQueryDesc& d, bool repl, bool occ8) {
+  ReplLayout layout;
+  const ReplLayout* L = repl && planRepl(d, &layout) ? &layout : nullptr;
   // raw slot bound (same rule as the interpreted launcher)
   int maxSlot = -1;
   for (int f = 0; f < d.nFetch; f++)
@@ -443,8 +552,11 @@ std::string generateSource(const FusedQueryDesc& d) {
   std::ostringstream s;
   s << "#include \"gx_common.h\"\n#include \"gx_device.h\"\n"
        "using namespace gxp;\nusing RawT = " << rawT << ";\n\n";
+  if (L)
+    s << "constexpr int kReplSlots = " << L->S << ", kReplCopies = " << L->R
+      << ", kReplWords = " << L->W << ";\n\n";
   emitFetch(s, d);
-  emitRowPipe(s, d);
+  emitRowPipe(s, d, L);
   // kernel wrapper: same prologue/pipeline/epilogue as fusedAggKernel
   s << R"(
 template <bool WIDE>
@@ -455,7 +567,21 @@ __device__ __forceinline__ void kernBody(const FusedQueryDesc* __restrict__ dp) 
                         __HIP_MEMORY_SCOPE_AGENT))
     return;
   bool failed = false;
-  __shared__ GroupSlot lds[kLdsGroups];
+)";
+  if (L)
+    s << R"(  __shared__ uint64_t ldsKeys[kReplSlots];
+  __shared__ uint64_t ldsAcc[kReplSlots * kReplWords * kReplCopies];
+  Lds3U64* lkeys = (Lds3U64*)ldsKeys;
+  // this lane's copy: folded into the base once, not per row
+  Lds3U64* lacc = (Lds3U64*)ldsAcc + (threadIdx.x & (kReplCopies - 1));
+  for (int i = threadIdx.x; i < kReplSlots; i += blockDim.x)
+    ldsKeys[i] = kEmptyKey;
+  for (int i = threadIdx.x; i < kReplSlots * kReplWords * kReplCopies;
+       i += blockDim.x)
+    ldsAcc[i] = 0;
+)";
+  else
+    s << R"(  __shared__ GroupSlot lds[kLdsGroups];
   Lds3GroupSlot* lds3 = (Lds3GroupSlot*)lds;
   for (int i = threadIdx.x; i < kLdsGroups; i += blockDim.x) {
     lds[i].key = kEmptyKey;
@@ -465,7 +591,9 @@ __device__ __forceinline__ void kernBody(const FusedQueryDesc* __restrict__ dp) 
       lds[i].cnt[a] = 0;
     }
   }
-  __syncthreads();
+)";
+  const char* ldsArgs = L ? "lkeys, lacc" : "lds3";
+  s << R"(  __syncthreads();
   int64_t n = d.table.nRows;
   int64_t per = (n + gridDim.x - 1) / gridDim.x;
   int64_t begin = (int64_t)blockIdx.x * per;
@@ -480,10 +608,10 @@ __device__ __forceinline__ void kernBody(const FusedQueryDesc* __restrict__ dp) 
     for (; row < end && !failed; row += 2 * stride) {
       const int64_t rB = row + stride;
       if (rB < end) fetchGen(d.table, rB, rawB);
-      if (!rowPipe<WIDE>(d, row, rawA, lds3, &mySel)) { failed = true; break; }
+      if (!rowPipe<WIDE>(d, row, rawA, )" << ldsArgs << R"(, &mySel)) { failed = true; break; }
       const int64_t rA2 = row + 2 * stride;
       if (rA2 < end) fetchGen(d.table, rA2, rawA);
-      if (rB < end && !rowPipe<WIDE>(d, rB, rawB, lds3, &mySel)) failed = true;
+      if (rB < end && !rowPipe<WIDE>(d, rB, rawB, )" << ldsArgs << R"(, &mySel)) failed = true;
     }
   }
   if (d.selCount) {
@@ -494,9 +622,10 @@ __device__ __forceinline__ void kernBody(const FusedQueryDesc* __restrict__ dp) 
       atomicAdd((unsigned long long*)d.selCount, (unsigned long long)total);
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < kLdsGroups; i += blockDim.x) {
-    if (lds[i].key == kEmptyKey) continue;
-    uint64_t key = lds[i].key;
+  for (int i = threadIdx.x; i < )" << (L ? "kReplSlots" : "kLdsGroups")
+    << R"(; i += blockDim.x) {
+    uint64_t key = )" << (L ? "ldsKeys[i]" : "lds[i].key") << R"(;
+    if (key == kEmptyKey) continue;
     uint32_t gmask = (1u << d.globalGroupsLog2) - 1;
     uint32_t slot = (uint32_t)(splitmix64(key) & gmask);
     bool ok = true;
@@ -513,7 +642,40 @@ __device__ __forceinline__ void kernBody(const FusedQueryDesc* __restrict__ dp) 
       slot = (slot + 1) & gmask;
     }
     if (!ok) continue;
-    for (int s2 = 0; s2 < d.nAccSlots; s2++) {
+)";
+  if (L) {
+    // fold the copies of each word (sums as 128-bit values, counts add,
+    // biased min/max takes the maximum: zero is the identity of all three),
+    // then ONE global update per word, as the single-copy flush does
+    s << "    const uint64_t* g = &ldsAcc[i * (kReplWords * kReplCopies)];\n";
+    for (int sIdx = 0; sIdx < d.nAccSlots; sIdx++) {
+      const int w = L->accWord[sIdx];
+      if (d.accKind[sIdx] != 0) {
+        s << "    { uint64_t m = 0;\n"
+             "      for (int c = 0; c < kReplCopies; c++) { uint64_t x = g["
+          << w << " * kReplCopies + c]; if (x > m) m = x; }\n"
+             "      accumMax(&d.globalTable[slot], " << sIdx << ", m); }\n";
+      } else {
+        s << "    { Int128 v = {0, 0};\n"
+             "      for (int c = 0; c < kReplCopies; c++) {\n"
+             "        uint64_t lo = g[" << w << " * kReplCopies + c];\n"
+             "        uint64_t nl = v.lo + lo;\n"
+             "        v.hi = (int64_t)((uint64_t)v.hi + g[" << (w + 1)
+          << " * kReplCopies + c] + (nl < lo ? 1 : 0));\n"
+             "        v.lo = nl;\n"
+             "      }\n"
+             "      accumInto(&d.globalTable[slot], " << sIdx << ", v, 0); }\n";
+      }
+    }
+    const int nCnt = d.sharedCnt ? 1 : d.nAggs;
+    for (int a = 0; a < nCnt; a++)
+      s << "    { uint64_t c2 = 0;\n"
+           "      for (int c = 0; c < kReplCopies; c++) c2 += g["
+        << L->cntWord[a] << " * kReplCopies + c];\n"
+           "      accumInto(&d.globalTable[slot], " << a
+        << ", Int128{0, 0}, (int64_t)c2); }\n";
+  } else {
+    s << R"(    for (int s2 = 0; s2 < d.nAccSlots; s2++) {
       if (d.accKind[s2] != 0) {
         accumMax(&d.globalTable[slot], s2, lds[i].accLo[s2]);
         continue;
@@ -524,10 +686,14 @@ __device__ __forceinline__ void kernBody(const FusedQueryDesc* __restrict__ dp) 
     int nCnt = d.sharedCnt ? 1 : d.nAggs;
     for (int a = 0; a < nCnt; a++)
       accumInto(&d.globalTable[slot], a, Int128{0, 0}, lds[i].cnt[a]);
+)";
   }
+  s << R"(  }
 }
 
-extern "C" __global__ void __launch_bounds__(256) genq_narrow(const FusedQueryDesc* __restrict__ dp) {
+extern "C" __global__ void __launch_bounds__(256) )"
+    << (occ8 ? "__attribute__((amdgpu_waves_per_eu(8))) " : "")
+    << R"(genq_narrow(const FusedQueryDesc* __restrict__ dp) {
   kernBody<false>(dp);
 }
 extern "C" __global__ void __launch_bounds__(256) genq_wide(const FusedQueryDesc* __restrict__ dp) {
@@ -535,6 +701,14 @@ extern "C" __global__ void __launch_bounds__(256) genq_wide(const FusedQueryDesc
 }
 )";
   return s.str();
+}
+
+// The replicated narrow kernel asks for 8 waves per SIMD (<= 64 VGPRs, what
+// the single-copy kernels of the measured plans get on their own): its second
+// LDS base and copy offset cost the wide-projection plan 6 VGPRs and one wave
+// otherwise. compile() drops the request when it makes the kernel spill.
+std::string generateSource(const FusedQueryDesc& d, bool repl) {
+  return genSource(d, repl, repl);
 }
 
 // hipRTC-compile `src` for gfx950 and load the code object; nullptr (and
@@ -592,7 +766,8 @@ static const JitProg* compileSource(const std::string& src, const char* fn1,
   return prog.ok ? &slot : nullptr;
 }
 
-const JitProg* compile(const FusedQueryDesc& d, std::string* whyNot) {
+const JitProg* compile(const FusedQueryDesc& d, bool repl,
+                       std::string* whyNot) {
   for (int s = 0; s < d.nAccSlots; s++)
     if (d.accKind[s] == 3) {  // f64 atomics: interpreted kernel only
       if (whyNot) *whyNot = "f64 accumulator not specialized";
@@ -613,7 +788,24 @@ const JitProg* compile(const FusedQueryDesc& d, std::string* whyNot) {
       if (whyNot) *whyNot = "disjunctive filter not specialized";
       return nullptr;
     }
-  return compileSource(generateSource(d), "genq_narrow", "genq_wide", whyNot);
+  if (repl) {
+    ReplLayout L;
+    if (!planRepl(d, &L)) {
+      if (whyNot) *whyNot = "no replicated LDS layout for this plan";
+      return nullptr;
+    }
+  }
+  const JitProg* prog = compileSource(genSource(d, repl, repl), "genq_narrow",
+                                      "genq_wide", whyNot);
+  if (prog && repl) {
+    int scratch = 0;
+    if (hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES,
+                            prog->fnNarrow) != hipSuccess ||
+        scratch > 0)
+      prog = compileSource(genSource(d, true, false), "genq_narrow",
+                           "genq_wide", whyNot);
+  }
+  return prog;
 }
 
 int launch(const JitProg* prog, bool wide, const FusedQueryDesc* devDesc,

@@ -8,10 +8,16 @@ struct JitProg;
 // compile (process-cached) a specialized fused-agg kernel for this plan;
 // nullptr (with *whyNot set) on any failure -- caller falls back to the
 // interpreted kernel
-const JitProg* compile(const gxp::FusedQueryDesc& d, std::string* whyNot);
+// repl = the lane-replicated LDS layout (first accumulation tier): a small
+// key table whose accumulators have R copies; a block that meets more keys
+// than it holds raises kErrLdsSmall and the engine reruns with repl = false
+const JitProg* compile(const gxp::FusedQueryDesc& d, bool repl,
+                       std::string* whyNot);
+// group slots of the replicated layout for this plan (0 = it has none)
+int replSlots(const gxp::FusedQueryDesc& d);
 int launch(const JitProg* prog, bool wide, const gxp::FusedQueryDesc* devDesc,
            int grid, void* stream);
-std::string generateSource(const gxp::FusedQueryDesc& d);
+std::string generateSource(const gxp::FusedQueryDesc& d, bool repl);
 // join-aggregate probe kernel specialization
 const JitProg* compileJa(const gxp::JoinAggDesc& d, std::string* whyNot);
 int launchJa(const JitProg* prog, bool wide, const gxp::JoinAggDesc* devDesc,

@@ -544,6 +544,29 @@ __global__ void initGlobalTableKernel(GroupSlot* table, int64_t n) {
   }
 }
 
+// One thread per bank-0 slot: an occupied slot (folded with banks 1+ when
+// the noLds pass wrote them) is appended to out->slots through the header's
+// cursor. A flagged pass is retried or fails on the host: nothing to append.
+__launch_bounds__(256)
+__global__ void compactGroupsKernel(const FusedQueryDesc* __restrict__ dp,
+                                    int usedBanks, FusedResultBlock* out) {
+  const FusedQueryDesc& d = *dp;
+  if (out->hdr.errorFlag != 0) return;
+  const int64_t nSlots1 = (int64_t)1 << d.globalGroupsLog2;
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nSlots1) return;
+  const GroupSlot* src = &d.globalTable[i];
+  if (src->key == kEmptyKey) return;
+  uint32_t at = atomicAdd(&out->hdr.nOccupied, 1u);
+  if (at >= (uint32_t)kResultCap) return;
+  GroupSlot rec = *src;
+  const int nCnt = d.sharedCnt ? 1 : d.nAggs;
+  for (int bank = 1; bank < usedBanks; bank++)
+    foldGroupSlot(rec, d.globalTable[bank * nSlots1 + i], d.nAccSlots,
+                  d.accKind, nCnt);
+  out->slots[at] = rec;
+}
+
 
 // ==================================================================
 // join-aggregate pipeline (Q3 class) — see gx_common.h JoinAggDesc
@@ -1609,11 +1632,22 @@ int gxLaunchInitTable(GroupSlot* table, int64_t nSlots, void* stream) {
   return (int)hipGetLastError();
 }
 
+int gxLaunchCompactGroups(const FusedQueryDesc* devDesc, int globalGroupsLog2,
+                          int usedBanks, FusedResultBlock* out, void* stream) {
+  const int64_t nSlots1 = (int64_t)1 << globalGroupsLog2;
+  hipLaunchKernelGGL(compactGroupsKernel, dim3((int)((nSlots1 + 255) / 256)),
+                     dim3(256), 0, (hipStream_t)stream, devDesc, usedBanks,
+                     out);
+  return (int)hipGetLastError();
+}
+
 int gxLaunchFusedAgg(const FusedQueryDesc& desc, const FusedQueryDesc* devDesc,
                      void* stream, int skipInit) {
   hipStream_t s = (hipStream_t)stream;
   int grid = gxFusedGrid(desc.table.nRows);
-  int64_t nSlots = (int64_t)(1 << desc.globalGroupsLog2) * desc.accBanks;
+  // banks beyond 0 are written (and later read) only by a noLds pass
+  int64_t nSlots = (int64_t)(1 << desc.globalGroupsLog2) *
+                   (desc.noLds ? desc.accBanks : 1);
   if (!skipInit) {  // out-of-core slices accumulate into the SAME table
     hipLaunchKernelGGL(initGlobalTableKernel, dim3((int)((nSlots + 255) / 256)),
                        dim3(256), 0, s, desc.globalTable, nSlots);
