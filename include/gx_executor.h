@@ -318,6 +318,13 @@ int64_t gx_last_sel_count(gx_exec* ex);
  * 0 while every decimal still reads the 40-byte form). */
 const char* gx_debug_jit_source(gx_exec* ex);
 int32_t gx_debug_dec_units_cols(gx_exec* ex);
+/* product engine only, debug: bytes per row (1, 2, 4 or 8) of the units column
+ * that serves source column `col` of the fused table or of the join-agg probe
+ * table; 0 when that column is not served from units. And the number of rows
+ * per lane per load of the kernel that ran the last fused pass (1 for the
+ * interpreted kernels, 0 before any pass). */
+int32_t gx_debug_dec_units_width(gx_exec* ex, int32_t col);
+int32_t gx_debug_rows_per_lane(gx_exec* ex);
 /* product engine only, debug: the accumulation tier that answered the last
  * fused pass -- 0 lane-replicated LDS accumulators (generated kernels), 1 the
  * single 64-slot LDS table, 2 global-direct; -1 before any pass. And the

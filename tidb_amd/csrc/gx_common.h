@@ -11,6 +11,7 @@
 #include <cstdint>
 
 #include "gx_like.h"
+#include "gx_units.h"
 
 namespace gxp {
 
@@ -19,11 +20,13 @@ struct DevCol {
   void* data = nullptr;          // fixed: N*elem; varlen: bytes
   uint8_t* nullBitmap = nullptr; // LSB-first, 1 = NOT NULL; null => no NULLs
   int64_t* offsets = nullptr;    // varlen: N+1
-  // decimal col of a resident table: int64 units at the declared frac, one
-  // per row (NULL rows hold 0). Built once at bind, and only when every
-  // non-NULL row was proven to parse to exactly these units at exactly the
-  // declared frac (gxBuildDecUnits); null => read the 40 B form.
-  int64_t* units = nullptr;
+  // decimal col of a resident table: the units at the declared frac, one
+  // two's-complement value of unitsWidth bytes per row (NULL rows hold 0).
+  // Built once at bind, and only when every non-NULL row was proven to parse
+  // to exactly these units at exactly the declared frac (gxBuildDecUnits);
+  // the width is the narrowest of 1/2/4/8 B holding the proven range
+  // (gx_units.h). null => read the 40 B form.
+  void* units = nullptr;
   int32_t elemSize = 8;          // -1 varlen
   int32_t type = 0;              // gx type
   int32_t frac = 0;
@@ -31,6 +34,7 @@ struct DevCol {
   // varlen col whose offsets are the identity (offsets[i] == i, i.e. 1 byte
   // per row — char(1)): the scan needs no offsets reads. Proven at bind time.
   uint8_t denseOffsets = 0;
+  uint8_t unitsWidth = 8;        // bytes per row of `units`: 1, 2, 4 or 8
 };
 
 constexpr int kMaxCols = 16;
@@ -151,9 +155,10 @@ enum FetchKind : int32_t {
   FETCH_8B_CHAR2 = 4, // x = 8-byte element; y = 1-2 dense char(1) cols packed
                       // (plain kernel: prefetches group chars with the row)
   FETCH_CHAR2 = 5,    // y = 1-2 dense char(1) cols packed; x unused
-  FETCH_UNITS8 = 6,   // 8 bytes at units[row]: x = int64 units at the column's
-                      // declared frac, y = 0 (a FETCH_DEC16 slot rewritten in
-                      // place at bind for a column whose units were proven)
+  FETCH_UNITS8 = 6,   // unitsWidth bytes at units[row], sign-extended: x =
+                      // int64 units at the column's declared frac, y = 0 (a
+                      // FETCH_DEC16 slot rewritten in place at bind for a
+                      // column whose units were proven)
 };
 
 struct FetchDesc {
@@ -710,8 +715,13 @@ int gxFusedGrid(int64_t rows);
 // declaredFrac (0 for NULL rows). *flag becomes nonzero unless EVERY non-NULL
 // row has a valid header, digitsFrac == declaredFrac exactly, and units that
 // fit int64 -- the proof that lets the scan serve the column from `out`.
+// flag[1] receives the largest width class (unitsWidthOf: 1, 2, 4 or 8) any
+// non-NULL row needs; it stays 0 when no such row exists.
 int gxBuildDecUnits(const DevCol& col, int64_t nRows, int declaredFrac,
                     int64_t* out, uint32_t* flag, void* stream);
+// out[row] = in[row] at `width` (1, 2 or 4) bytes; every value must fit
+int gxNarrowUnits(const int64_t* in, int64_t nRows, int width, void* out,
+                  void* stream);
 int gxLaunchInitTable(GroupSlot* table, int64_t nSlots, void* stream);
 // append the occupied slots of the pass's global table to `out` (whose header
 // is the pass's flag/count block); usedBanks > 1 folds the noLds banks

@@ -266,6 +266,25 @@ struct RawState5 {
   }
 };
 
+// units of one row of a proven decimal column, sign-extended from the
+// column's width: the ONE at-use reader of DevCol::units outside generated
+// code (which carries the width as a literal typed load)
+__device__ inline int64_t loadUnits(const DevCol& c, int64_t row) {
+  switch (c.unitsWidth) {
+    case 1: return gptr<int8_t>(c.units)[row];
+    case 2: return gptr<int16_t>(c.units)[row];
+    case 4: return gptr<int32_t>(c.units)[row];
+    default: return gptr<int64_t>(c.units)[row];
+  }
+}
+
+// one aligned K-row load of a packed stream (generated blocked kernels):
+// T is the unsigned type of K * width bytes, `row` is K-aligned
+template <typename T>
+__device__ __forceinline__ T blkLoad(const void* base, int64_t row, int width) {
+  return *gptr<T>((const uint8_t*)base + row * width);
+}
+
 // phase A: issue every fetch for one row, no consumption (loads overlap).
 // The loop is unrolled over the compile-time slot bound so every raw.set has
 // a literal index — a runtime-indexed store would be re-rolled into scratch.
@@ -293,7 +312,7 @@ __device__ __attribute__((always_inline)) inline void fetchRow(const DevTable& t
       v.x = *gptr<uint64_t>(p);
       v.y = *gptr<uint64_t>(p + 8);
     } else if (fd.kind == FETCH_UNITS8) {
-      v.x = (uint64_t)gptr<int64_t>(c.units)[row];
+      v.x = (uint64_t)loadUnits(c, row);
       v.y = 0;
     } else {  // FETCH_OFFSETS
       v.x = (uint64_t)gptr<int64_t>(c.offsets)[row];

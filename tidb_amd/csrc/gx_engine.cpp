@@ -450,6 +450,7 @@ struct gx_exec {
   // decimal columns currently served from DevCol::units (buildDecUnits):
   // fused table / join-agg probe table
   int decUnitsFused = 0, decUnitsJa = 0;
+  int lastRowsPerLane = 0;  // gx_debug_rows_per_lane: 0 before any fused pass
   // standalone Selection (compact survivors of a CNF over one source)
   bool isSelect = false;
   JoinStage selStage;  // probe side only (srcP); hj.post = the CNF
@@ -2764,14 +2765,56 @@ static int64_t tableSchemaBytes(const gxp::DevTable& tab) {
   return rb * tab.nRows;
 }
 
+// Second pass of a proven units column whose range fits `width` < 8 bytes
+// (DESIGN.md §4i): copy it into a buffer of that width and free the int64
+// one. Never an error: on any failure the column keeps its int64 buffer.
+static void narrowDecUnits(gx_exec* ex, gxp::DevCol& c, int64_t nRows,
+                           int width, bool dbg, int colNo) {
+  void* narrow = devAllocP(ex, (size_t)gxp::unitsAllocBytes(nRows, width));
+  if (!narrow) {
+    (void)hipGetLastError();
+    return;
+  }
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (dbg) {
+    hipEventCreate(&e0);
+    hipEventCreate(&e1);
+    hipEventRecord(e0, ex->stream);
+  }
+  bool ok = gxp::gxNarrowUnits((const int64_t*)c.units, nRows, width, narrow,
+                               ex->stream) == 0;
+  if (dbg) hipEventRecord(e1, ex->stream);
+  ok = ok && hipStreamSynchronize(ex->stream) == hipSuccess;
+  if (dbg) {
+    float ms = 0;
+    if (ok) hipEventElapsedTime(&ms, e0, e1);
+    fprintf(stderr, "[gx] dec units col %d: width %d B%s, narrowing %.3f ms\n",
+            colNo, ok ? width : 8, ok ? "" : " (narrowing failed)", ms);
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+  }
+  if (!ok) {
+    (void)hipGetLastError();
+    devFreeP(ex, narrow);
+    return;
+  }
+  devFreeP(ex, c.units);
+  c.units = narrow;
+  c.unitsWidth = (uint8_t)width;
+}
+
 // Decimal units columns. `tab` is a RESIDENT source table
 // (generator or bound chunks: filled once, re-read by every later open), so
 // the 40 B -> int64 conversion the scan repeats per row per query is done
 // here once. Each listed column gets an 8 B/row buffer filled by
-// gxBuildDecUnits; a column whose proof fails keeps units == nullptr and its
-// 40 B path. Never an error: a short budget, a failed allocation or a failed
-// launch all leave the query exactly where it was. Returns the number of
-// columns now served from units.
+// gxBuildDecUnits, then narrowed to the width its proven range needs
+// (narrowDecUnits; GX_NO_UNITS_NARROW=1 keeps 8 B); a column whose proof
+// fails keeps units == nullptr and its 40 B path. The budget admits the
+// 8 B/row/column form; while one column is being narrowed its new buffer (at
+// most 4 B/row) is live on top of that, and a failed allocation there just
+// keeps the int64 buffer. Never an error: a short
+// budget, a failed allocation or a failed launch all leave the query exactly
+// where it was. Returns the number of columns now served from units.
 static int buildDecUnits(gx_exec* ex, gxp::DevTable& tab,
                          const std::vector<int>& cols, int64_t residentBytes) {
   if (cols.empty() || tab.nRows <= 0 || getenv("GX_NO_DEC_UNITS")) return 0;
@@ -2788,11 +2831,12 @@ static int buildDecUnits(gx_exec* ex, gxp::DevTable& tab,
               (long long)need, (long long)budget);
     return 0;
   }
-  uint32_t* flags = (uint32_t*)devAllocP(ex, cols.size() * 4);
+  // per column: {proof flag, width class of the non-NULL units}
+  uint32_t* flags = (uint32_t*)devAllocP(ex, cols.size() * 8);
   if (!flags) return 0;
   std::vector<int64_t*> bufs(cols.size(), nullptr);
   std::vector<hipEvent_t> evs(cols.size() + 1, nullptr);
-  bool ok = hipMemsetAsync(flags, 0, cols.size() * 4, ex->stream) == hipSuccess;
+  bool ok = hipMemsetAsync(flags, 0, cols.size() * 8, ex->stream) == hipSuccess;
   for (size_t i = 0; i < cols.size() && ok; i++) {
     bufs[i] = (int64_t*)devAllocP(ex, (size_t)tab.nRows * 8);
     ok = bufs[i] != nullptr;
@@ -2804,17 +2848,18 @@ static int buildDecUnits(gx_exec* ex, gxp::DevTable& tab,
   }
   for (size_t i = 0; i < cols.size() && ok; i++) {
     const gxp::DevCol& c = tab.cols[cols[i]];
-    ok = gxp::gxBuildDecUnits(c, tab.nRows, c.frac, bufs[i], flags + i,
+    ok = gxp::gxBuildDecUnits(c, tab.nRows, c.frac, bufs[i], flags + 2 * i,
                               ex->stream) == 0;
     if (ok && dbg) hipEventRecord(evs[i + 1], ex->stream);
   }
-  std::vector<uint32_t> hflags(cols.size(), 1u);
+  std::vector<uint32_t> hflags(cols.size() * 2, 1u);
   ok = ok && hipStreamSynchronize(ex->stream) == hipSuccess &&
-       hipMemcpy(hflags.data(), flags, cols.size() * 4,
+       hipMemcpy(hflags.data(), flags, cols.size() * 8,
                  hipMemcpyDeviceToHost) == hipSuccess;
+  const bool mayNarrow = getenv("GX_NO_UNITS_NARROW") == nullptr;
   int built = 0;
   for (size_t i = 0; i < cols.size(); i++) {
-    bool proven = ok && hflags[i] == 0;
+    bool proven = ok && hflags[2 * i] == 0;
     if (dbg && ok) {
       float ms = 0;
       hipEventElapsedTime(&ms, evs[i], evs[i + 1]);
@@ -2823,7 +2868,13 @@ static int buildDecUnits(gx_exec* ex, gxp::DevTable& tab,
               proven ? "compacted" : "kept 40 B (proof failed)", ms);
     }
     if (proven) {
-      tab.cols[cols[i]].units = bufs[i];
+      gxp::DevCol& c = tab.cols[cols[i]];
+      c.units = bufs[i];
+      c.unitsWidth = 8;
+      // the width class is one of 0 (no non-NULL row), 1, 2, 4, 8
+      const int width = hflags[2 * i + 1] <= 1 ? 1 : (int)hflags[2 * i + 1];
+      if (mayNarrow && width < 8) narrowDecUnits(ex, c, tab.nRows, width, dbg,
+                                                 cols[i]);
       built++;
     } else if (bufs[i]) {
       devFreeP(ex, bufs[i]);
@@ -3135,6 +3186,9 @@ static const gxjit::JitProg* fusedPickJit(gx_exec* ex, bool mayCompile) {
     prog = ex->jitProg;
   }
   ex->lastLdsTier = ex->desc.noLds ? 2 : (repl ? 0 : 1);
+  // what the pass's kernel does, not what the plan would allow: the
+  // interpreted kernels take one row per lane
+  ex->lastRowsPerLane = prog ? gxjit::progRowsPerLane(prog) : 1;
   return prog;
 }
 
@@ -6930,6 +6984,22 @@ const char* gx_debug_vm_program(gx_exec* ex) {
 // table + join-agg probe); 0 when every decimal still reads the 40 B form
 int32_t gx_debug_dec_units_cols(gx_exec* ex) {
   return ex ? ex->decUnitsFused + ex->decUnitsJa : 0;
+}
+
+// debug: bytes per row of source column `col`'s units column in the fused
+// table or the join-agg probe table; 0 when it is not served from units
+int32_t gx_debug_dec_units_width(gx_exec* ex, int32_t col) {
+  if (!ex || col < 0 || col >= gxp::kMaxCols) return 0;
+  const gxp::DevCol& c =
+      (ex->isJoinAgg ? ex->ja.probe : ex->desc.table).cols[col];
+  return c.units ? c.unitsWidth : 0;
+}
+
+// debug: rows per lane per load of the kernel that ran the last fused pass
+// (recorded when its source was generated; 1 for the interpreted kernels,
+// 0 before any pass)
+int32_t gx_debug_rows_per_lane(gx_exec* ex) {
+  return ex ? ex->lastRowsPerLane : 0;
 }
 
 // debug: accumulation tier of the last fused pass -- 0 lane-replicated LDS

@@ -16,11 +16,13 @@
 #include <hip/hiprtc.h>
 
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
 #include <sstream>
 #include <string>
+#include <vector>
 
 #include "gx_common.h"
 #include "gx_jit.h"
@@ -34,6 +36,7 @@ struct JitProg {
   hipFunction_t fnNarrow = nullptr;
   hipFunction_t fnWide = nullptr;
   bool ok = false;
+  int rowsPerLane = 1;  // fused-agg programs: K of the generated row loop
 };
 
 static std::map<std::string, JitProg>& cache() {
@@ -500,6 +503,179 @@ static void emitRowPipe(std::ostringstream& s, const FusedQueryDesc& d,
   s << "  }\n  return true;\n}\n\n";
 }
 
+// width of the units column behind a FETCH_UNITS8 slot (8 unless narrowed)
+static int unitsWidth(const FusedQueryDesc& d, int col) {
+  const int w = d.table.cols[col].unitsWidth;
+  return w == 1 || w == 2 || w == 4 ? w : 8;
+}
+
+// Rows a lane takes per load in the generated kernel: K
+// consecutive rows from a K-aligned row, each stream fetched with ONE load of
+// K * width bytes. Only where every fetch slot has a blocked form: units of
+// any width, 8 B columns and the dense char(1) pair; a plan with an offsets
+// pair or a 40 B decimal slot keeps one row per lane.
+int progRowsPerLane(const JitProg* prog) { return prog ? prog->rowsPerLane : 1; }
+
+int rowsPerLane(const FusedQueryDesc& d) {
+  int k = 4;
+  if (const char* e = getenv("GX_ROWS_PER_LANE")) k = atoi(e);
+  if (k != 2 && k != 4) return 1;
+  bool any = false;
+  for (int f = 0; f < d.nFetch; f++) {
+    const int kind = d.fetch[f].kind;
+    if (kind == gxp::FETCH_B1) continue;
+    if (kind == gxp::FETCH_OFFSETS || kind == gxp::FETCH_DEC16) return 1;
+    any = true;
+  }
+  return any ? k : 1;
+}
+
+// one packed stream of the blocked fetch: K values of `width` bytes
+struct BlkStream {
+  std::string name;  // member of BlkT
+  std::string base;  // column buffer expression
+  int width;
+};
+
+// the j-th 32-bit word of a stream's K-row load
+static std::string blkWord(const BlkStream& st, int K, int j) {
+  const int bytes = K * st.width;
+  static const char* xyzw[] = {".x", ".y", ".z", ".w"};
+  if (bytes <= 4) return "(uint32_t)b." + st.name;
+  if (bytes <= 16) return "b." + st.name + xyzw[j];
+  return "b." + st.name + (j < 4 ? "" : "_h") + xyzw[j & 3];
+}
+
+static const char* blkType(int bytes) {
+  return bytes == 2 ? "uint16_t" : bytes == 4 ? "uint32_t"
+         : bytes == 8 ? "uint2" : "uint4";
+}
+
+// Blocked form of emitFetch: BlkT holds one K-row load per stream, fetchBlk
+// issues them, unpackBlk<k> rebuilds row k's raw slots -- the same slot
+// values the one-row fetchGen produces, so rowPipe does not change.
+static void emitFetchBlk(std::ostringstream& s, const FusedQueryDesc& d,
+                         int K) {
+  std::vector<BlkStream> streams;
+  // per fetch slot: index of its value stream and of its char streams
+  int valueOf[gxp::kMaxFetch], chr0[gxp::kMaxFetch], chr1[gxp::kMaxFetch];
+  for (int f = 0; f < d.nFetch; f++) {
+    const gxp::FetchDesc& fd = d.fetch[f];
+    valueOf[f] = chr0[f] = chr1[f] = -1;
+    if (fd.kind == gxp::FETCH_B1) continue;
+    const std::string n = "s" + std::to_string(f);
+    auto col = [](int c, const char* m) {
+      return "t.cols[" + std::to_string(c) + "]." + m;
+    };
+    if (fd.kind == gxp::FETCH_8B || fd.kind == gxp::FETCH_8B_CHAR2) {
+      valueOf[f] = (int)streams.size();
+      streams.push_back({n, col(fd.col, "data"), 8});
+    } else if (fd.kind == gxp::FETCH_UNITS8) {
+      valueOf[f] = (int)streams.size();
+      streams.push_back({n, col(fd.col, "units"), unitsWidth(d, fd.col)});
+    }
+    if (fd.kind == gxp::FETCH_8B_CHAR2 || fd.kind == gxp::FETCH_CHAR2) {
+      chr0[f] = (int)streams.size();
+      streams.push_back({n + "_c0", col(fd.ldsOff & 0xFF, "data"), 1});
+      if (((fd.ldsOff >> 16) & 0xFF) > 1) {
+        chr1[f] = (int)streams.size();
+        streams.push_back({n + "_c1", col((fd.ldsOff >> 8) & 0xFF, "data"), 1});
+      }
+    }
+  }
+  s << "constexpr int kRowsPerLane = " << K << ";\nstruct BlkT {\n";
+  for (const BlkStream& st : streams) {
+    const int bytes = K * st.width;
+    s << "  " << blkType(bytes) << " " << st.name;
+    if (bytes == 32) s << ", " << st.name << "_h";
+    s << ";\n";
+  }
+  s << "};\n"
+       "// every K-row load is aligned when its column buffer is\n"
+       "__device__ __forceinline__ bool blkAligned(const DevTable& t) {\n"
+       "  uintptr_t a = 0;\n";
+  for (const BlkStream& st : streams)
+    s << "  a |= (uintptr_t)" << st.base << ";\n";
+  s << "  return (a & 15) == 0;\n}\n"
+       "__device__ __forceinline__ void fetchBlk(const DevTable& t, "
+       "int64_t row, BlkT& b) {\n";
+  for (const BlkStream& st : streams) {
+    const int bytes = K * st.width;
+    s << "  b." << st.name << " = blkLoad<" << blkType(bytes) << ">("
+      << st.base << ", row, " << st.width << ");\n";
+    if (bytes == 32)
+      s << "  b." << st.name << "_h = blkLoad<uint4>(" << st.base << ", row + "
+        << K / 2 << ", " << st.width << ");\n";
+  }
+  s << "}\n";
+  auto chr = [&](const BlkStream& st, int k) {
+    return "((" + blkWord(st, K, k >> 2) + " >> " + std::to_string(8 * (k & 3)) +
+           ") & 0xFFu)";
+  };
+  for (int k = 0; k < K; k++) {
+    s << "__device__ __forceinline__ void unpackBlk" << k
+      << "(const BlkT& b, RawT& r) {\n";
+    for (int f = 0; f < d.nFetch; f++) {
+      const gxp::FetchDesc& fd = d.fetch[f];
+      if (fd.kind == gxp::FETCH_B1) continue;
+      const std::string m = "r.s" + std::to_string(f);
+      s << "  " << m << ".x = ";
+      if (valueOf[f] < 0) {
+        s << "0;\n";
+      } else {
+        const BlkStream& st = streams[valueOf[f]];
+        s << "(uint64_t)";
+        if (st.width == 1)
+          s << "unitsUnpack1(" << blkWord(st, K, k >> 2) << ", " << (k & 3)
+            << ");\n";
+        else if (st.width == 2)
+          s << "unitsUnpack2(" << blkWord(st, K, k >> 1) << ", " << (k & 1)
+            << ");\n";
+        else if (st.width == 4)
+          s << "unitsUnpack4(" << blkWord(st, K, k) << ");\n";
+        else
+          s << "unitsUnpack8(" << blkWord(st, K, 2 * k) << ", "
+            << blkWord(st, K, 2 * k + 1) << ");\n";
+      }
+      s << "  " << m << ".y = ";
+      if (chr0[f] < 0) {
+        s << "0;\n";
+      } else {
+        s << "(uint64_t)(" << chr(streams[chr0[f]], k);
+        if (chr1[f] >= 0) s << " | (" << chr(streams[chr1[f]], k) << " << 8)";
+        s << ");\n";
+      }
+    }
+    s << "}\n";
+  }
+  s << "\n";
+}
+
+// run the K rows of one lane's block through rowPipe: from the block's loads
+// when it lies inside [begin, end) whole, else (the fewer than K rows at the
+// end of the table, or a column buffer that is not 16 B aligned) row by row
+// through the one-row fetch
+static void emitRunBlk(std::ostringstream& s, int K, bool repl) {
+  const char* ldsParams =
+      repl ? "Lds3U64* lkeys, Lds3U64* lacc" : "Lds3GroupSlot* lds";
+  const char* ldsArgs = repl ? "lkeys, lacc" : "lds";
+  s << "template <bool WIDE>\n"
+       "__device__ __forceinline__ bool runBlk(const FusedQueryDesc& d, "
+       "int64_t row, int64_t end, bool vec, const BlkT& b, "
+    << ldsParams << ", uint64_t* mySel) {\n"
+       "  RawT r;\n"
+       "  if (vec && row + kRowsPerLane <= end) {\n";
+  for (int k = 0; k < K; k++)
+    s << "    unpackBlk" << k << "(b, r);\n"
+      << "    if (!rowPipe<WIDE>(d, row + " << k << ", r, " << ldsArgs
+      << ", mySel)) return false;\n";
+  s << "    return true;\n  }\n"
+       "  for (int64_t x = row; x < end && x < row + kRowsPerLane; x++) {\n"
+       "    fetchGen(d.table, x, r);\n"
+       "    if (!rowPipe<WIDE>(d, x, r, " << ldsArgs << ", mySel)) return false;\n"
+       "  }\n  return true;\n}\n\n";
+}
+
 // literal fetch of every raw slot for one row
 static void emitFetch(std::ostringstream& s, const FusedQueryDesc& d) {
   s << "__device__ __forceinline__ void fetchGen(const DevTable& t, "
@@ -529,7 +705,9 @@ static void emitFetch(std::ostringstream& s, const FusedQueryDesc& d) {
         << "    " << m << ".x = *gptr<uint64_t>(p); " << m
         << ".y = *gptr<uint64_t>(p + 8); }\n";
     } else if (fd.kind == gxp::FETCH_UNITS8) {
-      s << "  " << m << ".x = (uint64_t)gptr<int64_t>(t.cols[" << fd.col
+      // the proven width as a literal typed load, sign-extended to the slot
+      s << "  " << m << ".x = (uint64_t)(int64_t)gptr<int"
+        << 8 * unitsWidth(d, fd.col) << "_t>(t.cols[" << fd.col
         << "].units)[row]; " << m << ".y = 0;\n";
     } else {  // FETCH_OFFSETS
       s << "  " << m << ".x = (uint64_t)gptr<int64_t>(t.cols[" << fd.col
@@ -555,8 +733,11 @@ static std::string genSource(const FusedQueryDesc& d, bool repl, bool occ8) {
   if (L)
     s << "constexpr int kReplSlots = " << L->S << ", kReplCopies = " << L->R
       << ", kReplWords = " << L->W << ";\n\n";
+  const int K = rowsPerLane(d);
   emitFetch(s, d);
+  if (K > 1) emitFetchBlk(s, d, K);
   emitRowPipe(s, d, L);
+  if (K > 1) emitRunBlk(s, K, L != nullptr);
   // kernel wrapper: same prologue/pipeline/epilogue as fusedAggKernel
   s << R"(
 template <bool WIDE>
@@ -596,11 +777,34 @@ __device__ __forceinline__ void kernBody(const FusedQueryDesc* __restrict__ dp) 
   s << R"(  __syncthreads();
   int64_t n = d.table.nRows;
   int64_t per = (n + gridDim.x - 1) / gridDim.x;
-  int64_t begin = (int64_t)blockIdx.x * per;
+)";
+  if (K > 1)  // every block begins at a K-aligned row
+    s << "  per = (per + kRowsPerLane - 1) / kRowsPerLane * kRowsPerLane;\n";
+  s << R"(  int64_t begin = (int64_t)blockIdx.x * per;
   int64_t end = begin + per;
   if (end > n) end = n;
   uint64_t mySel = 0;
-  {
+)";
+  if (K > 1)
+    // two-deep pipeline over blocks of K rows per lane
+    s << R"(  {
+    const bool vec = blkAligned(d.table);
+    const int64_t stride = (int64_t)blockDim.x * kRowsPerLane;
+    int64_t row = begin + (int64_t)threadIdx.x * kRowsPerLane;
+    BlkT blkA, blkB;
+    if (vec && row + kRowsPerLane <= end) fetchBlk(d.table, row, blkA);
+    for (; row < end && !failed; row += 2 * stride) {
+      const int64_t rB = row + stride;
+      if (vec && rB + kRowsPerLane <= end) fetchBlk(d.table, rB, blkB);
+      if (!runBlk<WIDE>(d, row, end, vec, blkA, )" << ldsArgs << R"(, &mySel)) { failed = true; break; }
+      const int64_t rA2 = row + 2 * stride;
+      if (vec && rA2 + kRowsPerLane <= end) fetchBlk(d.table, rA2, blkA);
+      if (rB < end && !runBlk<WIDE>(d, rB, end, vec, blkB, )" << ldsArgs << R"(, &mySel)) failed = true;
+    }
+  }
+)";
+  else
+    s << R"(  {
     const int64_t stride = blockDim.x;
     int64_t row = begin + threadIdx.x;
     RawT rawA, rawB;
@@ -614,7 +818,8 @@ __device__ __forceinline__ void kernBody(const FusedQueryDesc* __restrict__ dp) 
       if (rB < end && !rowPipe<WIDE>(d, rB, rawB, )" << ldsArgs << R"(, &mySel)) failed = true;
     }
   }
-  if (d.selCount) {
+)";
+  s << R"(  if (d.selCount) {
     uint64_t total = mySel;
     for (int off = 32; off > 0; off >>= 1)
       total += __shfl_down(total, off, 64);
@@ -707,8 +912,14 @@ extern "C" __global__ void __launch_bounds__(256) genq_wide(const FusedQueryDesc
 // the single-copy kernels of the measured plans get on their own): its second
 // LDS base and copy offset cost the wide-projection plan 6 VGPRs and one wave
 // otherwise. compile() drops the request when it makes the kernel spill.
+// The K-row form holds two blocks of loads in registers and is known to
+// spill at 64 VGPRs, so only the one-row form makes the request.
+static bool wantOcc8(const FusedQueryDesc& d, bool repl) {
+  return repl && rowsPerLane(d) == 1;
+}
+
 std::string generateSource(const FusedQueryDesc& d, bool repl) {
-  return genSource(d, repl, repl);
+  return genSource(d, repl, wantOcc8(d, repl));
 }
 
 // hipRTC-compile `src` for gfx950 and load the code object; nullptr (and
@@ -750,11 +961,13 @@ static hipModule_t compileModule(const std::string& src, const char* name,
 
 // compile (cached by source text); returns nullptr on any failure
 static const JitProg* compileSource(const std::string& src, const char* fn1,
-                                    const char* fn2, std::string* whyNot) {
+                                    const char* fn2, std::string* whyNot,
+                                    int rowsPerLane = 1) {
   std::lock_guard<std::mutex> lk(cacheMu);
   auto it = cache().find(src);
   if (it != cache().end()) return it->second.ok ? &it->second : nullptr;
   JitProg prog;
+  prog.rowsPerLane = rowsPerLane;
   prog.mod = compileModule(src, "genq.cu", whyNot);
   if (prog.mod &&
       hipModuleGetFunction(&prog.fnNarrow, prog.mod, fn1) == hipSuccess &&
@@ -795,15 +1008,17 @@ const JitProg* compile(const FusedQueryDesc& d, bool repl,
       return nullptr;
     }
   }
-  const JitProg* prog = compileSource(genSource(d, repl, repl), "genq_narrow",
-                                      "genq_wide", whyNot);
-  if (prog && repl) {
+  const bool occ8 = wantOcc8(d, repl);
+  const int K = rowsPerLane(d);
+  const JitProg* prog = compileSource(genSource(d, repl, occ8), "genq_narrow",
+                                      "genq_wide", whyNot, K);
+  if (prog && occ8) {
     int scratch = 0;
     if (hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES,
                             prog->fnNarrow) != hipSuccess ||
         scratch > 0)
       prog = compileSource(genSource(d, true, false), "genq_narrow",
-                           "genq_wide", whyNot);
+                           "genq_wide", whyNot, K);
   }
   return prog;
 }
@@ -843,10 +1058,13 @@ static void emitJaVm(std::ostringstream& s, const JoinAggDesc& d) {
           s << "  " << nv << " = colIsNull(d.probe.cols[" << ins.a
             << "], row);\n";
         if (c.units) {
-          // proven column: int64 units at the declared frac (= ins.b)
+          // proven column: units at the declared frac (= ins.b), read at
+          // use at the column's width
+          const int w = c.unitsWidth == 1 || c.unitsWidth == 2 ||
+                                c.unitsWidth == 4 ? c.unitsWidth : 8;
           s << "  if (!" << nv << ") " << v
-            << " = VT<WIDE>::fromI64(gptr<int64_t>(d.probe.cols[" << ins.a
-            << "].units)[row], nullptr);\n";
+            << " = VT<WIDE>::fromI64((int64_t)gptr<int" << 8 * w
+            << "_t>(d.probe.cols[" << ins.a << "].units)[row], nullptr);\n";
           break;
         }
         s << "  if (!" << nv << ") { int sc;\n";

@@ -15,6 +15,11 @@ const JitProg* compile(const gxp::FusedQueryDesc& d, bool repl,
                        std::string* whyNot);
 // group slots of the replicated layout for this plan (0 = it has none)
 int replSlots(const gxp::FusedQueryDesc& d);
+// rows a lane of the generated kernel takes per load for this plan (1 = the
+// one-row loop; GX_ROWS_PER_LANE picks 1, 2 or 4)
+int rowsPerLane(const gxp::FusedQueryDesc& d);
+// rows per lane the compiled program was generated with
+int progRowsPerLane(const JitProg* prog);
 int launch(const JitProg* prog, bool wide, const gxp::FusedQueryDesc* devDesc,
            int grid, void* stream);
 std::string generateSource(const gxp::FusedQueryDesc& d, bool repl);

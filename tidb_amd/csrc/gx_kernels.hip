@@ -886,8 +886,8 @@ __global__ void jaProbeKernel(const JoinAggDesc* __restrict__ dp) {
           bool nul = colIsNull(c, row);
           typename VT<WIDE>::T v = VT<WIDE>::zero();
           if (!nul && c.units) {
-            // proven column: int64 units at the declared frac (= ins.b)
-            v = VT<WIDE>::fromI64(gptr<int64_t>(c.units)[row], nullptr);
+            // proven column: units at the declared frac (= ins.b)
+            v = VT<WIDE>::fromI64(loadUnits(c, row), nullptr);
           } else if (!nul) {
             int sc;
             bool okp = ins.c >= 0
@@ -1571,17 +1571,21 @@ int gxFusedGrid(int64_t rows) {
 // header, digitsFrac != declaredFrac, units beyond int64) only raises the
 // flag -- no error moves to bind time; the engine drops the buffer and the
 // column keeps its FETCH_DEC16 path with every error surface where it was.
+// flag[1] collects the width class the non-NULL units need (gx_units.h): a
+// per-wave maximum, at most one atomic per wave.
 __launch_bounds__(256)
 __global__ void buildDecUnitsKernel(DevCol col, int64_t nRows, int declaredFrac,
                                     int64_t* __restrict__ out, uint32_t* flag) {
   const int64_t p10v = kP10(declaredFrac);
   const uint64_t magic = kDivMagic(9 - declaredFrac);
   bool bad = false;
+  int wcls = 0;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        row < nRows; row += stride) {
     int64_t units = 0;
-    if (!colIsNull(col, row)) {
+    const bool nul = colIsNull(col, row);
+    if (!nul) {
       const uint8_t* p = (const uint8_t*)col.data + row * 40;
       uint64_t w0 = *gptr<uint64_t>(p);
       uint64_t w1 = *gptr<uint64_t>(p + 8);
@@ -1611,9 +1615,29 @@ __global__ void buildDecUnitsKernel(DevCol col, int64_t nRows, int declaredFrac,
       }
     }
     out[row] = units;
+    if (!nul) {
+      const int w = unitsWidthOf(units);
+      if (w > wcls) wcls = w;
+    }
   }
   // at most one atomic per failing wave
   if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
+  // the classes are 1, 2, 4, 8: the wave's maximum is the top bit of their OR
+  uint32_t wave = (uint32_t)wcls;
+  for (int off = 32; off > 0; off >>= 1) wave |= __shfl_xor(wave, off, 64);
+  if (wave && (threadIdx.x & 63) == 0)
+    atomicMax(flag + 1, 1u << (31 - __clz(wave)));
+}
+
+// second bind-time pass of a units column whose proven range fits 1, 2 or
+// 4 bytes: one 8 B load and one narrow store per row
+__launch_bounds__(256)
+__global__ void narrowUnitsKernel(const int64_t* __restrict__ in,
+                                  int64_t nRows, int width, void* out) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       row < nRows; row += stride)
+    unitsStore(out, width, row, gptr<int64_t>(in)[row]);
 }
 
 int gxBuildDecUnits(const DevCol& col, int64_t nRows, int declaredFrac,
@@ -1622,6 +1646,14 @@ int gxBuildDecUnits(const DevCol& col, int64_t nRows, int declaredFrac,
   hipLaunchKernelGGL(buildDecUnitsKernel, dim3(gxFusedGrid(nRows)), dim3(256),
                      0, (hipStream_t)stream, col, nRows, declaredFrac, out,
                      flag);
+  return (int)hipGetLastError();
+}
+
+int gxNarrowUnits(const int64_t* in, int64_t nRows, int width, void* out,
+                  void* stream) {
+  if (width != 1 && width != 2 && width != 4) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(narrowUnitsKernel, dim3(gxFusedGrid(nRows)), dim3(256), 0,
+                     (hipStream_t)stream, in, nRows, width, out);
   return (int)hipGetLastError();
 }
 
