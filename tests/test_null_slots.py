@@ -106,7 +106,25 @@ def _chunk(lib, types, fracs, rows):
 ROW_KEY = lambda r: tuple((x is None, x) for x in r)
 
 
-def _run(lib, scn, mode, is_oracle):
+def pull_cycles(ex, out_types, out_fracs, data_caps, opens):
+    """opens open/pull/close cycles on one executor; the rows of each. After
+    the first, one more cycle is opened, pulled for a single chunk and
+    closed, so the next one starts from a half-drained run."""
+    out = []
+    for cycle in range(opens):
+        if cycle == 1:
+            ex.open()
+            ex.pull_one(out_types, out_fracs, data_caps=data_caps)
+            ex.close()
+        ex.open()
+        out.append(ex.pull_all(out_types, out_fracs, data_caps=data_caps))
+        ex.close()
+    return out
+
+
+def _run(lib, scn, mode, is_oracle, opens=None):
+    """opens=None: the rows of one open. opens=k: a list of k row lists, one
+    per open/pull/close cycle on the same executor (pull_cycles)."""
     b = P.Builder(lib)
     srcs = [b.source(t, f) for t, f, _ in scn.tables]
     root, out_types, out_fracs = scn.plan(b, lib, srcs, is_oracle)
@@ -123,14 +141,14 @@ def _run(lib, scn, mode, is_oracle):
                 assert count_null_slots(ch, c) >= 8, (scn.name, ti, c)
         chunks.append(ch)
         ex.bind_chunks(srcs[ti], [ch])
-    ex.open()
-    rows = ex.pull_all(out_types, out_fracs,
-                       data_caps=[1 << 16 if t == STR else None
-                                  for t in out_types])
-    ex.close()
+    cycles = pull_cycles(ex, out_types, out_fracs,
+                         [1 << 16 if t == STR else None for t in out_types],
+                         opens or 1)
     ex.free()
     b.free()
-    return rows if scn.ordered else sorted(rows, key=ROW_KEY)
+    if not scn.ordered:
+        cycles = [sorted(rows, key=ROW_KEY) for rows in cycles]
+    return cycles[0] if opens is None else cycles
 
 
 _WANT = {}
@@ -167,14 +185,19 @@ def _check_oracle(scn, mode):
     assert _run(load_oracle(), scn, mode, True) == _want(scn)  # bit-exact
 
 
-def _check_product(scn, mode, monkeypatch):
+def _check_product(scn, mode, monkeypatch, opens=None):
+    """opens=k: k cycles on one executor, each equal to the oracle's single
+    open."""
     monkeypatch.setenv("GX_DEBUG", "1")
-    for var in ("GX_NO_JIT", "GX_FORCE_WIDE", "GX_GLDS", "GX_HBM_BUDGET"):
+    for var in ("GX_NO_JIT", "GX_FORCE_WIDE", "GX_GLDS", "GX_HBM_BUDGET",
+                "GX_SORT_RUN_ROWS"):
         if var in scn.env:
             monkeypatch.setenv(var, scn.env[var])
         else:
             monkeypatch.delenv(var, raising=False)
-    _assert_same(_run(load_product(), scn, mode, False), _want(scn), scn)
+    got = _run(load_product(), scn, mode, False, opens)
+    for rows in [got] if opens is None else got:
+        _assert_same(rows, _want(scn), scn)
 
 
 def _maybe(rng, v):
@@ -281,7 +304,7 @@ def test_topn_slice(tname, mode, monkeypatch):
 
 
 @functools.lru_cache(maxsize=None)
-def _join_sort_scn(desc):
+def _join_sort_scn(desc, limit=1000, offset=0):
     """ORDER BY (build payload, probe payload, id) above a left outer join
     (test_join_types._run_outer_sorted's shape): the first key is NULL both
     where the build row held a NULL and where the join null-extended."""
@@ -294,15 +317,17 @@ def _join_sort_scn(desc):
         j = b.hashjoin(srcs[0], srcs[1], [b.colref(0, I64)],
                        [b.colref(0, I64)], join_type=1)
         keys = [b.colref(c, I64) for c in (1, 3, 4)]
-        return b.topn(j, keys, [desc, desc, 0], 1000), [I64] * 5, [0] * 5
+        return (b.topn(j, keys, [desc, desc, 0], limit, offset), [I64] * 5,
+                [0] * 5)
 
-    return Scn(f"join-sort-{desc}",
+    tag = "" if (limit, offset) == (1000, 0) else f"-{limit}-{offset}"
+    return Scn(f"join-sort-{desc}{tag}",
                [([I64] * 2, [0] * 2, brows), ([I64] * 3, [0] * 3, prows)],
                plan, [(0, 1), (1, 0), (1, 1)], ordered=True)
 
 
 @functools.lru_cache(maxsize=None)
-def _sel_sort_scn(desc):
+def _sel_sort_scn(desc, limit=100, offset=0):
     """TopN above a Selection (test_selection's topn shape): c > 2 drops
     the rows whose c is NULL, then ORDER BY a, b, id LIMIT 100."""
     rng = np.random.default_rng(43)
@@ -315,9 +340,11 @@ def _sel_sort_scn(desc):
         sel = b.selection(srcs[0], [b.call(GX_F_GT, I64, 0, b.colref(3, I64),
                                            b.const_i64(2))])
         keys = [b.colref(c, types[c], fracs[c]) for c in (0, 1, 2)]
-        return b.topn(sel, keys, [desc, 1 - desc, 0], 100), types, fracs
+        return (b.topn(sel, keys, [desc, 1 - desc, 0], limit, offset), types,
+                fracs)
 
-    return Scn(f"sel-sort-{desc}", [(types, fracs, rows)], plan,
+    tag = "" if (limit, offset) == (100, 0) else f"-{limit}-{offset}"
+    return Scn(f"sel-sort-{desc}{tag}", [(types, fracs, rows)], plan,
                [(0, 0), (0, 1), (0, 3)], ordered=True)
 
 
@@ -686,15 +713,21 @@ JOIN_STRS = ["", "A", "A ", "xy", "BUILDING"]
 
 
 @functools.lru_cache(maxsize=None)
-def _join_tables(shape, build_nulls=True):
+def _join_tables(shape, build_nulls=True, empty=None):
     """build (keys.., payload), probe (keys.., payload, id); keys and
-    payloads nullable."""
+    payloads nullable. build_nulls=False drops the build rows whose first
+    key is NULL; "none" also fills the NULLs of the second key column, so no
+    build key column holds one; "single" is "none" with the first key of one
+    build row NULL. empty="build" / "probe" leaves that side
+    without rows."""
     rng = np.random.default_rng(59)
     nb, npr = 300, 900
     bk, pk = _join_keys(rng, nb, 40), _join_keys(rng, npr, 60)
-    if not build_nulls:
+    if build_nulls is not True:
         bk = [k for k in bk if k is not None]
         nb = len(bk)
+        if build_nulls == "single":
+            bk[nb // 2] = None
     bpay = [_maybe(rng, int(rng.integers(0, 50))) for _ in range(nb)]
     ppay = [_maybe(rng, int(rng.integers(0, 50))) for _ in range(npr)]
     if shape == "one":
@@ -706,6 +739,8 @@ def _join_tables(shape, build_nulls=True):
         kt, kf = [I64, I64], [0, 0]
         bs = [_maybe(rng, int(rng.integers(0, 2))) for _ in range(nb)]
         ps = [_maybe(rng, int(rng.integers(0, 2))) for _ in range(npr)]
+        if build_nulls in ("none", "single"):
+            bs = [i % 2 if v is None else v for i, v in enumerate(bs)]
         b2 = lambda i: (bk[i], bs[i])
         p2 = lambda i: (pk[i], ps[i])
         fb = fp = kf
@@ -714,22 +749,38 @@ def _join_tables(shape, build_nulls=True):
         kt, kf = [DEC, STR], [1, 0]
         bs = [_maybe(rng, JOIN_STRS[int(rng.integers(0, 5))]) for _ in range(nb)]
         ps = [_maybe(rng, JOIN_STRS[int(rng.integers(0, 5))]) for _ in range(npr)]
+        if build_nulls in ("none", "single"):
+            bs = [JOIN_STRS[i % 5] if v is None else v
+                  for i, v in enumerate(bs)]
         b2 = lambda i: (None if bk[i] is None else JOIN_DECS[bk[i]], bs[i])
         p2 = lambda i: (None if pk[i] is None else JOIN_DECS[pk[i]] + "0",
                         ps[i])
         fb, fp = [1, 0], [2, 0]
     brows = [b2(i) + (bpay[i],) for i in range(nb)]
     prows = [p2(i) + (ppay[i], i) for i in range(npr)]
+    if empty == "build":
+        brows = []
+    elif empty is not None:
+        assert empty == "probe"
+        prows = []
     return ((kt + [I64], fb + [0], brows), (kt + [I64, I64], fp + [0, 0], prows))
 
 
 @functools.lru_cache(maxsize=None)
-def _join_scn(shape, jt, build_nulls=True, other=False, budget=None):
-    (bt, bf, brows), (pt, pf, prows) = _join_tables(shape, build_nulls)
+def _join_scn(shape, jt, build_nulls=True, other=False, budget=None,
+              empty=None, build_pred=False):
+    """build_pred: the build side under a Selection (payload < 25), so the
+    null-aware joins' valid set is what passes it."""
+    (bt, bf, brows), (pt, pf, prows) = _join_tables(shape, build_nulls, empty)
     nk = len(bt) - 1
 
     def plan(b, lib, srcs, is_oracle):
-        root = b.hashjoin(srcs[0], srcs[1],
+        bside = srcs[0]
+        if build_pred:
+            bside = b.selection(bside, [b.call(GX_F_LT, I64, 0,
+                                               b.colref(nk, I64),
+                                               b.const_i64(25))])
+        root = b.hashjoin(bside, srcs[1],
                           [b.colref(c, bt[c], bf[c]) for c in range(nk)],
                           [b.colref(c, pt[c], pf[c]) for c in range(nk)],
                           join_type=jt)
@@ -746,10 +797,13 @@ def _join_scn(shape, jt, build_nulls=True, other=False, budget=None):
         return root, bt + pt, bf + pf
 
     fixed_keys = [c for c in range(nk) if bt[c] != STR]
-    nullable = [(0, c) for c in fixed_keys if build_nulls] + \
+    nullable = [(0, c) for c in fixed_keys if build_nulls is True] + \
         [(1, c) for c in fixed_keys] + [(0, nk), (1, nk)]
+    nullable = [(t, c) for t, c in nullable
+                if t != {"build": 0, "probe": 1}.get(empty)]
     env = {} if budget is None else {"GX_HBM_BUDGET": str(budget)}
-    return Scn(f"join-{shape}-{jt}-{build_nulls}-{other}",
+    tag = (f"-empty-{empty}" if empty else "") + ("-pred" if build_pred else "")
+    return Scn(f"join-{shape}-{jt}-{build_nulls}-{other}{tag}",
                [(bt, bf, brows), (pt, pf, prows)], plan, nullable, env=env)
 
 

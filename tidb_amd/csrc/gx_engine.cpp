@@ -359,6 +359,7 @@ struct gx_exec {
   size_t emitPos = 0;
   // bare-source emit state
   int64_t srcPos = 0;
+  int64_t sliceStart = 0;  // first row of the OFFSET/LIMIT slice, for re-open
   // device full sort over a bare source (sortexec/sort.go analog)
   std::vector<gxp::SortKeyCompose> devSortKeys;
   bool devSorted = false;
@@ -441,6 +442,9 @@ struct gx_exec {
   int joinSpillCur = -1;
   size_t joinSpillMark = SIZE_MAX;
   std::vector<JoinPart> spillB, spillP;
+  // null-aware joins (types 5, 7) under spill: passing build rows and NULL
+  // build keys of the WHOLE build side, summed while partitioning it
+  uint64_t spillBuildPass = 0, spillBuildNullKeys = 0;
   uint64_t joinSpillMatches = 0;
   gxp::HashJoinDesc* devHj = nullptr;
   // general aggregation over joined rows: runHashJoin materializes the join
@@ -4613,7 +4617,9 @@ static int32_t gatherColsAuto(gx_exec* ex, const gxp::DevTable& srcTab,
 // gather into st.out. Sides come from bound sources (materialized once) or
 // previous stages' outputs.
 static int32_t runJoinStage(gx_exec* ex, gx_exec::JoinStage& st, bool isRoot) {
-  gxp::HashJoinDesc& hj = st.hj;
+  // a per-run copy: the run's buffers and the effective join type a
+  // null-aware join settles on must not outlive it in st.hj
+  gxp::HashJoinDesc hj = st.hj;
   hj.build = st.srcB >= 0 ? st.buildTab : ex->joinStages[st.buildStage].out;
   hj.probe = st.srcP >= 0 ? st.probeTab : ex->joinStages[st.probeStage].out;
   int64_t nb = hj.build.nRows;
@@ -4678,6 +4684,10 @@ static int32_t runJoinStage(gx_exec* ex, gx_exec::JoinStage& st, bool isRoot) {
     uint64_t hstats[2] = {0, 0};
     HIP_OK(ex, hipStreamSynchronize(ex->stream));
     HIP_OK(ex, hipMemcpy(hstats, bstats, 16, hipMemcpyDeviceToHost));
+    if (ex->joinSpill) {  // hj.build is one partition: take the whole side's
+      hstats[0] = ex->spillBuildPass;
+      hstats[1] = ex->spillBuildNullKeys;
+    }
     if (hj.joinType == 5) {
       if (hstats[0] == 0) {
         hj.joinType = 4;  // empty valid set: every probe row qualifies
@@ -4888,6 +4898,7 @@ static int32_t partitionJoinSide(gx_exec* ex, gx_exec::JoinStage& st,
   Binding& b = ex->bindings[srcId];
   int nc = (int)srcN.colTypes.size();
   parts->assign(nParts, JoinPart{});
+  if (side == 0) ex->spillBuildPass = ex->spillBuildNullKeys = 0;
   for (auto& jp : *parts) {
     jp.colData.resize(nc);
     jp.colOffsets.resize(nc);
@@ -4898,12 +4909,14 @@ static int32_t partitionJoinSide(gx_exec* ex, gx_exec::JoinStage& st,
   const int64_t saveRows = b.tpchRows, saveOff = b.tpchRowOffset,
                 saveTot = b.tpchTotalRows;
   int64_t done = 0;
+  bool chunksDone = false;  // a chunk-bound side uploads once, rows or none
   int32_t rc = GX_OK;
   for (;;) {
     size_t mark = ex->devBufs.size();
     gxp::DevTable tab{};
     if (b.haveChunks) {
-      if (done > 0) break;
+      if (chunksDone) break;
+      chunksDone = true;
       rc = materializeTable(ex, srcId, &tab);
       if (rc) break;
       done = tab.nRows;
@@ -4940,6 +4953,22 @@ static int32_t partitionJoinSide(gx_exec* ex, gx_exec::JoinStage& st,
     }
     std::vector<uint32_t> pid(n);
     hipMemcpy(pid.data(), devPid, (size_t)n * 4, hipMemcpyDeviceToHost);
+    if (side == 0 && (st.hj.joinType == 5 || st.hj.joinType == 7)) {
+      // the null-aware joins' two build scalars cover the whole build side,
+      // not one partition: count them per slice while it is on the device
+      uint64_t* bstats = (uint64_t*)devAlloc(ex, 16);
+      uint64_t hstats[2] = {0, 0};
+      if (!bstats || hipMemsetAsync(bstats, 0, 16, ex->stream) != hipSuccess ||
+          gxp::gxHjBuildStats(ex->devHj, hj2, bstats, ex->stream) != 0 ||
+          hipStreamSynchronize(ex->stream) != hipSuccess ||
+          hipMemcpy(hstats, bstats, 16, hipMemcpyDeviceToHost) != hipSuccess) {
+        ex->err = "join build-stats launch failed";
+        rc = GX_ERR_INTERNAL;
+        break;
+      }
+      ex->spillBuildPass += hstats[0];
+      ex->spillBuildNullKeys += hstats[1];
+    }
     // download the slice
     std::vector<std::vector<uint8_t>> hData(nc);
     std::vector<std::vector<int64_t>> hOff(nc);
@@ -5025,7 +5054,12 @@ static int32_t uploadJoinPart(gx_exec* ex, const PNode& srcN,
       if (!jp.colData[c].empty())
         hipMemcpy(col.data, jp.colData[c].data(), jp.colData[c].size(),
                   hipMemcpyHostToDevice);
-      col.denseOffsets = jp.colOffsets[c].back() == n ? 1 : 0;
+      // dense = every value exactly one byte (offsets are the identity
+      // ramp), as uploadBoundChunks checks it; lengths {0, 2} also sum to n
+      bool dense = true;
+      for (int64_t i = 0; i <= n && dense; i++)
+        dense = jp.colOffsets[c][i] == i;
+      col.denseOffsets = dense ? 1 : 0;
     } else {
       col.data = devAlloc(ex, std::max<size_t>(jp.colData[c].size(), 1) + 16);
       if (!col.data) { ex->err = "hipMalloc failed"; return GX_ERR_INTERNAL; }
@@ -5836,7 +5870,7 @@ static int32_t runDeviceSort(gx_exec* ex) {
   hipEventDestroy(ev1);
   ex->devSorted = true;
   // offset/limit: serve the slice [offset, offset+limit)
-  ex->srcPos = std::min<int64_t>(ex->devSortOffset, n);
+  ex->srcPos = ex->sliceStart = std::min<int64_t>(ex->devSortOffset, n);
   if (ex->devSortLimit >= 0)
     tab.nRows = std::min<int64_t>(n, ex->srcPos + ex->devSortLimit);
   return GX_OK;
@@ -6140,7 +6174,7 @@ static void applyBareLimit(gx_exec* ex) {
   if (!ex->devSortKeys.empty() || ex->devSorted) return;
   if (ex->devSortLimit < 0 && ex->devSortOffset <= 0) return;
   int64_t n = ex->desc.table.nRows;
-  ex->srcPos = std::min<int64_t>(ex->devSortOffset, n);
+  ex->srcPos = ex->sliceStart = std::min<int64_t>(ex->devSortOffset, n);
   if (ex->devSortLimit >= 0)
     ex->desc.table.nRows = std::min<int64_t>(n, ex->srcPos + ex->devSortLimit);
   ex->devSorted = true;  // applied once
@@ -6830,6 +6864,9 @@ int32_t gx_open(gx_exec* ex) {
   // join/select/project re-runs rebuild desc.table from scratch (beginRun
   // frees the previous run's buffers), so a sort above them must re-run too
   if (ex->isHashJoin || ex->isSelect || ex->isProject) ex->devSorted = false;
+  // a bare source keeps its sorted (or limited) table, cut to offset + limit:
+  // emission restarts at the slice's first row, the sort does not rerun
+  if (ex->devSorted) ex->srcPos = ex->sliceStart;
   if (ex->spillSorted) {  // re-open: replay the merged runs from the top
     ex->runPos.assign(ex->sortRuns.size(), 0);
     ex->spillSkip = ex->devSortOffset;
