@@ -164,7 +164,38 @@ enum {
    * constant, the first argument is a column, the escape lies in 0..255,
    * at most 4 distinct value-context patterns per operator -- anything else
    * is GX_ERR_INVALID at plan compile. */
-  GX_F_LIKE = 54, GX_F_NOT_LIKE = 55
+  GX_F_LIKE = 54, GX_F_NOT_LIKE = 55,
+  /* composed string outputs, byte semantics (builtin_string_vec.go,
+   * builtin_cast_vec.go):
+   * CONCAT    (builtinConcatSig): n >= 1 args; NULL if ANY arg is NULL,
+   *           otherwise the args' bytes in order.
+   * CONCAT_WS (builtinConcatWSSig): args (separator, a1, ..., an), n >= 1;
+   *           the separator is a CONSTANT string (it may be empty). NULL
+   *           args are skipped together with their separator, empty strings
+   *           are not; with a constant separator the result is never NULL
+   *           (every arg NULL -> '').
+   * CAST_STR  (builtinCastIntAsStringSig, signed): one arg, any expression
+   *           the projection VM compiles to an i64 (a column, YEAR(t),
+   *           LENGTH(s), a + b, ...): its decimal text, '-' for negatives,
+   *           no padding (INT64_MIN -> the 20 bytes -9223372036854775808);
+   *           NULL propagates. Decimal, float, time and string args are
+   *           rejected; the ABI has no unsigned i64, so none is accepted. A
+   *           computed arg materializes as a hidden computed output that
+   *           counts toward the 16 computed outputs of a projection.
+   * An arg ("piece") of CONCAT / CONCAT_WS is a string column under a
+   * SUBSTR/UPPER/LOWER/TRIM chain (dense char(1) columns included), a
+   * constant string, CAST_STR(...), or -- inside CONCAT only -- a nested
+   * CONCAT, which flattens. CAST_STR(x) alone is a one-piece output.
+   * Valid ONLY as outputs of the standalone Projection over
+   * [Selection ->] Source: not as group, join or sort keys, not in
+   * predicates, and not under UPPER/LOWER/SUBSTR/TRIM/LENGTH/LIKE. Limits:
+   * at most 8 pieces per output after flattening, at most 256 bytes of
+   * string constants per operator (separators included), no CONCAT_WS
+   * nested in CONCAT or CONCAT_WS, one output row below 2 GiB -- anything
+   * else is GX_ERR_INVALID at plan compile (the row limit: an error at
+   * run). TiDB's max_allowed_packet truncation of the result (NULL plus a
+   * warning) is out of scope: results are never truncated. */
+  GX_F_CONCAT = 56, GX_F_CONCAT_WS = 57, GX_F_CAST_STR = 58
 };
 
 /* ---- aggregate function codes (pkg/executor/aggfuncs) ---- */
@@ -341,6 +372,17 @@ int32_t gx_debug_result_compact(gx_exec* ex);
  * fetch table, LIKE pattern count. Valid after gx_build, no GPU needed; the
  * string is overwritten by the next call. */
 const char* gx_debug_vm_program(gx_exec* ex);
+/* product engine only, debug (not part of the stable ABI), no GPU needed:
+ * evaluates composed string output `out_col` (a CONCAT / CONCAT_WS /
+ * CAST_STR output of a built standalone Projection) over ONE host chunk of
+ * the projection's input schema, on the host, through the source the kernels
+ * run: length pass, prefix sum, then the byte mapping tile by tile. `out` is
+ * a caller-allocated string column (data_cap / offsets_cap honored, as in
+ * gx_next). A CAST_STR argument that is a plain column reads the chunk; a
+ * VM-computed one (YEAR(t), a + b, ...) returns GX_ERR_INVALID, as does an
+ * out_col that is not a composed string. */
+int32_t gx_debug_strcat_eval(gx_exec* ex, int32_t out_col, const gx_chunk* in,
+                             gx_col* out);
 
 /* ---- decimal helpers (each library's own implementation; used by golden
  * vector tests against pkg/types/mydecimal_test.go answers) ---- */

@@ -11,6 +11,7 @@
 #include <cstdint>
 
 #include "gx_like.h"
+#include "gx_strcat.h"
 #include "gx_units.h"
 
 namespace gxp {
@@ -667,9 +668,24 @@ struct ProjDesc {
   int32_t nSprog = 0;
   LikePat likePats[kMaxLikePats];  // VM_LIKE pattern table
   int32_t nLikePats = 0;
+  // composed string outputs (CONCAT / CONCAT_WS / CAST_STR, gx_strcat.h).
+  // These stay LAST: an upload ends after the programs in use
+  // (projDescUploadBytes, gx_engine.cpp).
+  int32_t nCat = 0;
+  int32_t catPoolLen = 0;  // bytes of catPool in use (host side)
+  uint8_t catPool[kStrCatPoolBytes];
+  StrCatProg cat[kMaxCols];
 };
+static_assert(kMaxStrWin == kStrCatMaxWin, "a piece holds a StrProg's windows");
 
 int gxProject(const ProjDesc* devDesc, const ProjDesc& h, void* stream);
+// composed string program catIdx: the length pass writes lens[row] and
+// notNull[row]; the emit pass copies bytes through the scanned offsets, one
+// block per 256-row tile, lanes striding over the tile's output bytes
+int gxStrCatLens(const ProjDesc* devDesc, const ProjDesc& h, int catIdx,
+                 int64_t* lens, uint8_t* notNull, void* stream);
+int gxStrCatEmit(const ProjDesc* devDesc, const ProjDesc& h, int catIdx,
+                 const int64_t* outOffsets, uint8_t* outData, void* stream);
 // string program: pass 1 computes per-row (start,len,notNull) views;
 // pass 2 copies the bytes through the scanned offsets (ASCII upcase opt.)
 int gxStrWindow(const ProjDesc* devDesc, const ProjDesc& h, int progIdx,

@@ -22,6 +22,7 @@ constexpr uint32_t kErrGlobalFull = 32u;
 // kernel holds: the engine reruns with the single-copy layout; not an error
 constexpr uint32_t kErrLdsSmall = 64u;
 constexpr uint32_t kErrRetryWide = 256u;  // narrow VM overflowed; not an error
+constexpr uint32_t kErrStrRowTooLong = 512u;  // composed row > kStrCatMaxRowBytes
 
 __host__ __device__ inline uint64_t splitmix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ULL;

@@ -13,6 +13,7 @@
 // of canonical partial states (KB-sized; MergePartialResult semantics,
 // aggfuncs.go:250-255).
 #include <hip/hip_runtime.h>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 
@@ -468,6 +469,7 @@ struct gx_exec {
   std::vector<int> projOutSrcCol;  // >=0 passthrough; -1 computed
   std::vector<int> projOutSprog;   // >=0 string program; -1 otherwise
   std::vector<int> projOutSlot;    // computed: index into pd.out*
+  std::vector<int> projOutCat;     // >=0 composed string program (pd.cat)
 
   ~gx_exec() {
     for (void* p : devBufs) hipFree(p);
@@ -626,6 +628,27 @@ static void beginRun(gx_exec* ex) {
 
 // ---------------- plan compilation ----------------
 
+// composed string calls (CONCAT / CONCAT_WS / CAST_STR): outputs of the
+// standalone Projection only, see compileStrCat
+static bool isComposedCall(const PExpr& e) {
+  return e.kind == EK_CALL && (e.func == GX_F_CONCAT ||
+                               e.func == GX_F_CONCAT_WS ||
+                               e.func == GX_F_CAST_STR);
+}
+
+static bool exprHasComposed(const PPlan& plan, int eid) {
+  if (eid < 0 || eid >= (int)plan.exprs.size()) return false;
+  const PExpr& e = plan.exprs[eid];
+  if (isComposedCall(e)) return true;
+  for (int a : e.args)
+    if (exprHasComposed(plan, a)) return true;
+  return false;
+}
+
+static const char* kComposedOverMsg =
+    "UPPER/LOWER/SUBSTR/TRIM/LENGTH/LIKE over a CONCAT, CONCAT_WS or CAST_STR "
+    "result is unsupported (apply them to the arguments instead)";
+
 // general LIKE / NOT LIKE call (GX_F_LIKE / GX_F_NOT_LIKE): args are
 // (string COLUMN, const string pattern [, const i64 escape byte]). Validates
 // them against the schema the call runs over and compiles the pattern
@@ -640,6 +663,10 @@ static bool compileLikeCall(gx_exec* ex, const PExpr& e,
   const PExpr& col = ex->plan.exprs[e.args[0]];
   const PExpr& pat = ex->plan.exprs[e.args[1]];
   int c = col.colIdx - colBase;
+  if (exprHasComposed(ex->plan, e.args[0])) {
+    ex->err = kComposedOverMsg;
+    return false;
+  }
   if (col.kind != EK_COLREF || c < 0 || c >= (int)colTypes.size() ||
       colTypes[c] != GX_TYPE_STRING) {
     ex->err = "device LIKE: the first argument must be a string column";
@@ -774,6 +801,10 @@ static int vmCompile(gx_exec* ex, ExprBuilder& B, int exprId, int* scaleOut) {
     }
     case EK_CALL: {
       if (e.func == GX_F_LENGTH) {  // builtinLengthSig: byte length -> i64
+        if (e.args.size() == 1 && exprHasComposed(ex->plan, e.args[0])) {
+          ex->err = kComposedOverMsg;
+          return -1;
+        }
         if (e.args.size() != 1 ||
             ex->plan.exprs[e.args[0]].kind != EK_COLREF) {
           ex->err = "device LENGTH takes one string column";
@@ -1737,6 +1768,212 @@ static bool compileStrProg(gx_exec* ex, int exprId,
   return false;
 }
 
+// ---- composed string outputs (CONCAT / CONCAT_WS / CAST_STR, gx_strcat.h) ----
+
+// composed strings exist only as outputs of the root Projection: anywhere
+// else in the tree (group, join and sort keys, predicates, aggregate
+// arguments, inner projections) they are a plan error
+static bool composedOnlyAtRootProjection(gx_exec* ex) {
+  const PPlan& plan = ex->plan;
+  std::vector<int> todo{ex->root};
+  std::set<int> seen;
+  while (!todo.empty()) {
+    int ni = todo.back();
+    todo.pop_back();
+    if (ni < 0 || ni >= (int)plan.nodes.size() || !seen.insert(ni).second)
+      continue;
+    const PNode& n = plan.nodes[ni];
+    todo.push_back(n.child);
+    todo.push_back(n.child2);
+    if (ni == ex->root && n.kind == PK_PROJECTION) continue;
+    bool bad = false;
+    for (const std::vector<int>* v :
+         {&n.exprs, &n.aggArgs, &n.buildKeys, &n.probeKeys})
+      for (int eid : *v) bad = bad || exprHasComposed(plan, eid);
+    if (bad) {
+      ex->err = "CONCAT / CONCAT_WS / CAST_STR are valid only as outputs of "
+                "the standalone Projection over [Selection ->] Source: not "
+                "as group keys, join keys, sort keys, aggregate arguments or "
+                "predicates";
+      return false;
+    }
+  }
+  return true;
+}
+
+// a constant into the operator's pool
+static bool catAddConst(gx_exec* ex, gxp::ProjDesc& pd, const std::string& s,
+                        uint16_t* off, uint16_t* len) {
+  if ((size_t)pd.catPoolLen + s.size() > (size_t)gxp::kStrCatPoolBytes) {
+    ex->err = "more than 256 bytes of string constants in one projection "
+              "(CONCAT / CONCAT_WS constants, separators included)";
+    return false;
+  }
+  std::memcpy(pd.catPool + pd.catPoolLen, s.data(), s.size());
+  *off = (uint16_t)pd.catPoolLen;
+  *len = (uint16_t)s.size();
+  pd.catPoolLen += (int32_t)s.size();
+  return true;
+}
+
+static bool catNewPiece(gx_exec* ex, gxp::StrCatProg* cp, gxp::StrPiece** out) {
+  if (cp->nPieces >= gxp::kStrCatMaxPieces) {
+    ex->err = "more than 8 pieces in one CONCAT / CONCAT_WS output (after "
+              "flattening nested CONCATs)";
+    return false;
+  }
+  *out = &cp->piece[cp->nPieces++];
+  **out = gxp::StrPiece{};
+  return true;
+}
+
+// CAST_STR(x): x is an i64 column (read in place) or an expression the
+// projection VM compiles to an i64, materialized as a hidden computed output
+static bool catAddCast(gx_exec* ex, ExprBuilder& B, gxp::ProjDesc& pd,
+                       const std::vector<int>& types, const PExpr& e,
+                       gxp::StrCatProg* cp) {
+  static const char* kArgMsg =
+      "CAST_STR takes one signed integer argument (decimal, float, time, "
+      "string and unsigned arguments are rejected)";
+  if (e.args.size() != 1) {
+    ex->err = kArgMsg;
+    return false;
+  }
+  const PExpr& a = ex->plan.exprs[e.args[0]];
+  bool i64 = a.retType == GX_TYPE_I64;
+  if (a.kind == EK_COLREF)
+    i64 = a.colIdx >= 0 && a.colIdx < (int)types.size() &&
+          types[a.colIdx] == GX_TYPE_I64;
+  if (!i64) {
+    ex->err = kArgMsg;
+    return false;
+  }
+  gxp::StrPiece* pc;
+  if (!catNewPiece(ex, cp, &pc)) return false;
+  pc->kind = gxp::SPK_I64;
+  if (a.kind == EK_COLREF) {
+    pc->col = (int16_t)a.colIdx;
+    return true;
+  }
+  int sc = 0;
+  int reg = vmCompile(ex, B, e.args[0], &sc);
+  if (reg < 0) {
+    if (ex->err.empty()) ex->err = "unsupported CAST_STR argument expression";
+    return false;
+  }
+  if (sc != 0) {
+    ex->err = kArgMsg;
+    return false;
+  }
+  if (pd.nOut >= gxp::kMaxCols) {
+    ex->err = "too many computed outputs (a computed CAST_STR argument is a "
+              "hidden one; 16 per projection)";
+    return false;
+  }
+  int o = pd.nOut++;
+  pd.outReg[o] = reg;
+  pd.outScale[o] = 0;
+  pd.outType[o] = GX_TYPE_I64;
+  pc->slot = (int16_t)o;
+  return true;
+}
+
+// one argument of CONCAT / CONCAT_WS -> piece(s) of cp
+static bool catAddArg(gx_exec* ex, ExprBuilder& B, gxp::ProjDesc& pd,
+                      const std::vector<int>& types, int argId,
+                      gxp::StrCatProg* cp) {
+  const PExpr& a = ex->plan.exprs[argId];
+  if (a.kind == EK_CONST) {
+    if (a.retType != GX_TYPE_STRING) {
+      ex->err = "CONCAT / CONCAT_WS arguments are strings (wrap an integer "
+                "in CAST_STR)";
+      return false;
+    }
+    gxp::StrPiece* pc;
+    if (!catNewPiece(ex, cp, &pc)) return false;
+    pc->kind = gxp::SPK_CONST;
+    return catAddConst(ex, pd, a.constStr, &pc->constOff, &pc->constLen);
+  }
+  if (a.kind == EK_CALL && a.func == GX_F_CAST_STR)
+    return catAddCast(ex, B, pd, types, a, cp);
+  if (a.kind == EK_CALL && a.func == GX_F_CONCAT_WS) {
+    ex->err = "CONCAT_WS nested inside CONCAT or CONCAT_WS is unsupported";
+    return false;
+  }
+  if (a.kind == EK_CALL && a.func == GX_F_CONCAT) {
+    if (cp->ws) {  // the NULL rules differ: it would not flatten
+      ex->err = "CONCAT nested inside CONCAT_WS is unsupported (a nested "
+                "CONCAT flattens inside CONCAT only)";
+      return false;
+    }
+    if (a.args.empty()) {
+      ex->err = "CONCAT takes at least one argument";
+      return false;
+    }
+    for (int sub : a.args)
+      if (!catAddArg(ex, B, pd, types, sub, cp)) return false;
+    return true;
+  }
+  gxp::StrProg sp{};
+  if (!compileStrProg(ex, argId, types, &sp)) {
+    // name the limit when the chain bottoms out in a composed string
+    int cur = argId;
+    while (ex->plan.exprs[cur].kind == EK_CALL &&
+           !isComposedCall(ex->plan.exprs[cur]) &&
+           !ex->plan.exprs[cur].args.empty())
+      cur = ex->plan.exprs[cur].args[0];
+    ex->err = isComposedCall(ex->plan.exprs[cur])
+                  ? kComposedOverMsg
+                  : "unsupported CONCAT / CONCAT_WS argument (a string column "
+                    "under SUBSTR/UPPER/LOWER/TRIM, a constant string, "
+                    "CAST_STR, or a nested CONCAT)";
+    return false;
+  }
+  gxp::StrPiece* pc;
+  if (!catNewPiece(ex, cp, &pc)) return false;
+  pc->kind = gxp::SPK_WINDOW;
+  pc->col = (int16_t)sp.col;
+  pc->caseOp = sp.upper ? gxp::SCO_UPPER
+                        : (sp.lower ? gxp::SCO_LOWER : gxp::SCO_NONE);
+  pc->nWin = (uint8_t)sp.nWin;
+  for (int w = 0; w < sp.nWin; w++) {
+    pc->winPos[w] = gxp::strWinSaturate(sp.winPos[w]);
+    pc->winLen[w] = gxp::strWinSaturate(sp.winLen[w]);
+  }
+  return true;
+}
+
+// a CONCAT / CONCAT_WS / CAST_STR projection output -> one StrCatProg
+static bool compileStrCat(gx_exec* ex, ExprBuilder& B, gxp::ProjDesc& pd,
+                          const std::vector<int>& types, int exprId,
+                          gxp::StrCatProg* cp) {
+  const PExpr& e = ex->plan.exprs[exprId];
+  *cp = gxp::StrCatProg{};
+  if (e.func == GX_F_CAST_STR) return catAddCast(ex, B, pd, types, e, cp);
+  size_t first = 0;
+  if (e.func == GX_F_CONCAT_WS) {
+    if (e.args.size() < 2) {
+      ex->err = "CONCAT_WS takes a separator and at least one argument";
+      return false;
+    }
+    const PExpr& sep = ex->plan.exprs[e.args[0]];
+    if (sep.kind != EK_CONST || sep.retType != GX_TYPE_STRING) {
+      ex->err = "the CONCAT_WS separator must be a constant string";
+      return false;
+    }
+    cp->ws = 1;
+    if (!catAddConst(ex, pd, sep.constStr, &cp->sepOff, &cp->sepLen))
+      return false;
+    first = 1;
+  } else if (e.args.empty()) {
+    ex->err = "CONCAT takes at least one argument";
+    return false;
+  }
+  for (size_t i = first; i < e.args.size(); i++)
+    if (!catAddArg(ex, B, pd, types, e.args[i], cp)) return false;
+  return true;
+}
+
 // standalone Projection over a Source or a Selection(Source)
 // (ProjectionExec, projection.go:77): computed expressions materialize as
 // device columns (decimal encode on device), passthrough colrefs alias the
@@ -1784,12 +2021,36 @@ static int32_t compileProject(gx_exec* ex) {
       ex->projOutSprog.push_back(-1);
       ex->projOutTypes.push_back((*childTypes)[e.colIdx]);
       ex->projOutFracs.push_back((*childFracs)[e.colIdx]);
+    } else if (isComposedCall(e)) {
+      // composed string outputs: pieces of several columns, constants and
+      // integer text (gx_strcat.h)
+      if (pd.nCat >= gxp::kMaxCols ||
+          !compileStrCat(ex, B, pd, *childTypes, eid, &pd.cat[pd.nCat])) {
+        if (ex->err.empty()) ex->err = "unsupported composed string projection";
+        return GX_ERR_INVALID;
+      }
+      ex->projOutSrcCol.push_back(-1);
+      ex->projOutSlot.push_back(-1);
+      ex->projOutSprog.push_back(-1);
+      ex->projOutTypes.push_back(GX_TYPE_STRING);
+      ex->projOutFracs.push_back(0);
+      ex->projOutCat.resize(ex->projOutTypes.size(), -1);
+      ex->projOutCat.back() = pd.nCat++;
     } else if (e.kind == EK_CALL && e.retType == GX_TYPE_STRING) {
       // string outputs: SUBSTR/UPPER chains fold into one windowed view
       gxp::StrProg sp{};
       if (!compileStrProg(ex, eid, *childTypes, &sp)) {
-        ex->err = "unsupported string projection (SUBSTR/UPPER/LOWER/TRIM chains over "
-                  "a string column this round)";
+        int cur = eid;
+        while (ex->plan.exprs[cur].kind == EK_CALL &&
+               !isComposedCall(ex->plan.exprs[cur]) &&
+               !ex->plan.exprs[cur].args.empty())
+          cur = ex->plan.exprs[cur].args[0];
+        ex->err = isComposedCall(ex->plan.exprs[cur])
+                      ? kComposedOverMsg
+                      : "unsupported string projection (SUBSTR/UPPER/LOWER/"
+                        "TRIM chains over a string column, or CONCAT / "
+                        "CONCAT_WS / CAST_STR of such chains, constants and "
+                        "integers)";
         return GX_ERR_INVALID;
       }
       int si = pd.nSprog++;
@@ -1807,6 +2068,11 @@ static int32_t compileProject(gx_exec* ex) {
         return GX_ERR_INVALID;
       }
       int outType = e.retType == GX_TYPE_I64 ? GX_TYPE_I64 : GX_TYPE_DECIMAL;
+      if (pd.nOut >= gxp::kMaxCols) {  // hidden CAST_STR arguments count too
+        ex->err = "too many computed outputs (a computed CAST_STR argument is "
+                  "a hidden one; 16 per projection)";
+        return GX_ERR_INVALID;
+      }
       int o = pd.nOut++;
       pd.outReg[o] = reg;
       pd.outScale[o] = sc;
@@ -1818,6 +2084,7 @@ static int32_t compileProject(gx_exec* ex) {
       ex->projOutFracs.push_back(outType == GX_TYPE_I64 ? 0 : sc);
     }
   }
+  ex->projOutCat.resize(ex->projOutTypes.size(), -1);
   // the projection kernel loads directly, in program order (no fetch
   // pipeline, no reorder)
   if (finishVmProgram(ex, B, 0) < 0) return GX_ERR_INVALID;
@@ -5320,6 +5587,13 @@ static int32_t runSelect(gx_exec* ex) {
 
 // ---------------- standalone projection execution ----------------
 
+// bytes of a ProjDesc the device reads: the composed string programs come
+// last, and the upload ends after the ones in use
+static size_t projDescUploadBytes(const gxp::ProjDesc& h) {
+  return offsetof(gxp::ProjDesc, cat) +
+         (size_t)h.nCat * sizeof(gxp::StrCatProg);
+}
+
 static int32_t runProject(gx_exec* ex) {
   gxp::ProjDesc& pd = ex->pd;
   if (!ex->projOverSelect) ex->lastKernelMs = 0;  // else runSelect seeds it
@@ -5396,6 +5670,58 @@ static int32_t runProject(gx_exec* ex) {
       return GX_ERR_INTERNAL;
     }
   }
+  // composed string programs: 9 B/row of lens + notNull, the offsets, and
+  // an output buffer sized from an upper bound computed in int64_t (a window
+  // never exceeds its column's bytes, an integer's text is <= 20 bytes), so
+  // nothing is read back inside the timed window
+  struct CatBufs {
+    int64_t* lens = nullptr;
+    uint8_t* notNull = nullptr;
+    int64_t* offsets = nullptr;
+    uint8_t* bitmap = nullptr;
+    void* data = nullptr;
+    void* tmp = nullptr;
+    size_t tmpBytes = 0;
+  };
+  std::vector<CatBufs> cat(pd.nCat);
+  std::map<int, int64_t> colBytes;  // string column -> total bytes
+  for (int ci = 0; ci < pd.nCat && n > 0; ci++) {
+    const gxp::StrCatProg& cp = pd.cat[ci];
+    int64_t bound = cp.ws ? n * (int64_t)(cp.nPieces - 1) * cp.sepLen : 0;
+    for (int p = 0; p < cp.nPieces; p++) {
+      const gxp::StrPiece& pc = cp.piece[p];
+      if (pc.kind == gxp::SPK_CONST) {
+        bound += n * (int64_t)pc.constLen;
+      } else if (pc.kind == gxp::SPK_I64) {
+        bound += n * 20;
+      } else {
+        auto it = colBytes.find(pc.col);
+        if (it == colBytes.end()) {
+          const gxp::DevCol& srcc = pd.table.cols[pc.col];
+          int64_t srcBytes = n;  // dense char(1)
+          if (!srcc.denseOffsets && srcc.offsets)
+            HIP_OK(ex, hipMemcpy(&srcBytes, srcc.offsets + n, 8,
+                                 hipMemcpyDeviceToHost));
+          it = colBytes.emplace(pc.col, srcBytes).first;
+        }
+        bound += it->second;
+      }
+    }
+    CatBufs& cb = cat[ci];
+    cb.lens = (int64_t*)devAlloc(ex, (size_t)n * 8);
+    cb.notNull = (uint8_t*)devAlloc(ex, (size_t)n);
+    cb.offsets = (int64_t*)devAlloc(ex, ((size_t)n + 1) * 8);
+    cb.bitmap = (uint8_t*)devAlloc(ex, (n + 7) / 8);
+    cb.data = devAlloc(ex, (size_t)std::max<int64_t>(bound, 1));
+    gxp::gxExclusiveSumI64(cb.lens, cb.offsets, n, nullptr, &cb.tmpBytes,
+                           ex->stream);
+    cb.tmp = devAlloc(ex, std::max<size_t>(cb.tmpBytes, 1));
+    if (!cb.lens || !cb.notNull || !cb.offsets || !cb.bitmap || !cb.data ||
+        !cb.tmp) {
+      ex->err = "hipMalloc failed";
+      return GX_ERR_INTERNAL;
+    }
+  }
   // the timed window covers the kernels, not the multi-GB hipMalloc churn
   hipEvent_t ev0, ev1;
   HIP_OK(ex, hipEventCreate(&ev0));
@@ -5403,7 +5729,7 @@ static int32_t runProject(gx_exec* ex) {
   HIP_OK(ex, hipEventRecord(ev0, ex->stream));
   for (int attempt = 0; n > 0 && attempt < 2; attempt++) {
     HIP_OK(ex, hipMemsetAsync(ex->devErr, 0, 4, ex->stream));
-    HIP_OK(ex, hipMemcpyAsync(ex->devPd, &pd, sizeof(pd),
+    HIP_OK(ex, hipMemcpyAsync(ex->devPd, &pd, projDescUploadBytes(pd),
                               hipMemcpyHostToDevice, ex->stream));
     if (gxp::gxProject(ex->devPd, pd, ex->stream) != 0) {
       ex->err = "projection kernel launch failed";
@@ -5450,6 +5776,28 @@ static int32_t runProject(gx_exec* ex) {
       return GX_ERR_INTERNAL;
     }
   }
+  // composed string programs: row lengths -> scanned offsets -> tile emit
+  // (hidden integer arguments were written by the projection kernel above)
+  for (int ci = 0; ci < pd.nCat && n > 0; ci++) {
+    CatBufs& cb = cat[ci];
+    if (gxp::gxStrCatLens(ex->devPd, pd, ci, cb.lens, cb.notNull,
+                          ex->stream) != 0) {
+      ex->err = "composed string length launch failed";
+      return GX_ERR_INTERNAL;
+    }
+    HIP_OK(ex, hipMemsetAsync(cb.offsets, 0, 8, ex->stream));
+    if (gxp::gxExclusiveSumI64(cb.lens, cb.offsets, n, cb.tmp, &cb.tmpBytes,
+                               ex->stream) != 0) {
+      ex->err = "string offsets scan failed";
+      return GX_ERR_INTERNAL;
+    }
+    if (gxp::gxStrCatEmit(ex->devPd, pd, ci, cb.offsets, (uint8_t*)cb.data,
+                          ex->stream) != 0 ||
+        gxp::gxPackNulls(cb.notNull, cb.bitmap, n, ex->stream) != 0) {
+      ex->err = "composed string emit launch failed";
+      return GX_ERR_INTERNAL;
+    }
+  }
   HIP_OK(ex, hipEventRecord(ev1, ex->stream));
   HIP_OK(ex, hipStreamSynchronize(ex->stream));
   {
@@ -5458,6 +5806,14 @@ static int32_t runProject(gx_exec* ex) {
     ex->lastKernelMs += ms;
     hipEventDestroy(ev0);
     hipEventDestroy(ev1);
+  }
+  if (pd.nCat > 0 && n > 0) {
+    uint32_t errFlag = 0;
+    HIP_OK(ex, hipMemcpy(&errFlag, ex->devErr, 4, hipMemcpyDeviceToHost));
+    if (errFlag & 512u /*kErrStrRowTooLong*/) {
+      ex->err = "a CONCAT / CONCAT_WS output row exceeds 2 GiB";
+      return GX_ERR_INVALID;
+    }
   }
   // assemble the output table: passthrough columns alias the input buffers
   ex->desc.table.nCols = (int)ex->projOutTypes.size();
@@ -5471,6 +5827,14 @@ static int32_t runProject(gx_exec* ex) {
       dst.data = n > 0 ? spData[si] : nullptr;
       dst.offsets = n > 0 ? spOffsets[si] : nullptr;
       dst.nullBitmap = n > 0 ? spBitmaps[si] : nullptr;
+      dst.hasNulls = n > 0 ? 1 : 0;
+      dst.denseOffsets = 0;
+    } else if (ex->projOutCat[c] >= 0) {
+      const CatBufs& cb = cat[ex->projOutCat[c]];
+      setDevColMeta(&dst, GX_TYPE_STRING, 0);
+      dst.data = cb.data;
+      dst.offsets = cb.offsets;
+      dst.nullBitmap = cb.bitmap;
       dst.hasNulls = n > 0 ? 1 : 0;
       dst.denseOffsets = 0;
     } else {
@@ -6485,6 +6849,7 @@ gx_exec* gx_build(gx_pb* pb, int32_t root, int32_t device) {
   ex->plan = pb->plan;
   ex->root = root;
   ex->device = device;
+  if (!composedOnlyAtRootProjection(ex)) return ex;
   const PNode& rn = ex->plan.nodes[root];
   if (rn.kind == PK_HASHAGG && rn.aggMode == GX_AGG_MODE_FINAL) {
     if (ex->plan.nodes[rn.child].kind != PK_SOURCE) {
@@ -7008,6 +7373,29 @@ const char* gx_debug_vm_program(gx_exec* ex) {
     dumpVmProgram(s, "probe", ex->ja, nLoads, -1, ex->ja.fetch, ex->ja.nFetch, 0);
   } else if (ex->isProject) {
     dumpVmProgram(s, "projection", ex->pd, 0, -1, nullptr, 0, ex->pd.nLikePats);
+    // composed string programs: a section of their own, only when present
+    for (int ci = 0; ci < ex->pd.nCat; ci++) {
+      const gxp::StrCatProg& cp = ex->pd.cat[ci];
+      char buf[256];
+      snprintf(buf, sizeof buf, "strcat[%d] nPieces=%d ws=%d sepOff=%d sepLen=%d\n",
+               ci, cp.nPieces, cp.ws, cp.sepOff, cp.sepLen);
+      s += buf;
+      for (int p = 0; p < cp.nPieces; p++) {
+        const gxp::StrPiece& pc = cp.piece[p];
+        snprintf(buf, sizeof buf,
+                 "piece[%d] kind=%d case=%d nWin=%d col=%d slot=%d constOff=%d "
+                 "constLen=%d\n",
+                 p, pc.kind, pc.caseOp, pc.nWin, pc.col, pc.slot, pc.constOff,
+                 pc.constLen);
+        s += buf;
+        for (int w = 0; w < pc.nWin; w++) {
+          snprintf(buf, sizeof buf, "win[%d] pos=%d len=%d\n", w, pc.winPos[w],
+                   pc.winLen[w]);
+          s += buf;
+        }
+      }
+    }
+    if (ex->pd.nCat > 0) s += "strcatPool=" + std::to_string(ex->pd.catPoolLen) + "\n";
   } else if (ex->isFused) {
     dumpVmProgram(s, "fused", ex->desc, ex->desc.nLoadIns, ex->desc.nVmRegs,
                   ex->desc.fetch, ex->desc.nFetch, ex->desc.nLikePats);
@@ -7015,6 +7403,68 @@ const char* gx_debug_vm_program(gx_exec* ex) {
     s = "site none\nerror: " + ex->err + "\n";
   }
   return s.c_str();
+}
+
+// debug: one composed string output over one host chunk, on the host, through
+// gx_strcat.h's passes (length, prefix sum, tile-by-tile byte mapping) --
+// the source the kernels run; no GPU needed
+int32_t gx_debug_strcat_eval(gx_exec* ex, int32_t out_col, const gx_chunk* in,
+                             gx_col* out) {
+  if (!ex || !in || !out) return GX_ERR_INVALID;
+  if (!ex->isProject || out_col < 0 || out_col >= (int)ex->projOutCat.size() ||
+      ex->projOutCat[out_col] < 0) {
+    ex->err = "gx_debug_strcat_eval: not a composed string output";
+    return GX_ERR_INVALID;
+  }
+  const gxp::ProjDesc& pd = ex->pd;
+  const gxp::StrCatProg& cp = pd.cat[ex->projOutCat[out_col]];
+  const std::vector<int>& types = ex->projOverSelect
+                                      ? ex->selStage.types
+                                      : ex->plan.nodes[ex->projSrcNode].colTypes;
+  if (in->n_cols != (int32_t)types.size() || in->n_rows < 0) {
+    ex->err = "gx_debug_strcat_eval: chunk does not match the input schema";
+    return GX_ERR_INVALID;
+  }
+  gxp::StrCatHostSrc src;
+  src.poolp = pd.catPool;
+  for (int p = 0; p < cp.nPieces; p++) {
+    const gxp::StrPiece& pc = cp.piece[p];
+    if (pc.kind == gxp::SPK_CONST) continue;
+    if (pc.col < 0) {
+      ex->err = "gx_debug_strcat_eval: a VM-computed CAST_STR argument needs "
+                "the device";
+      return GX_ERR_INVALID;
+    }
+    const gx_col& g = in->cols[pc.col];
+    src.nullBitmap[p] = g.null_bitmap;
+    if (pc.kind == gxp::SPK_I64) {
+      src.i64[p] = (const int64_t*)g.data;
+    } else {
+      src.data[p] = (const uint8_t*)g.data;
+      src.offsets[p] = g.offsets;
+    }
+  }
+  int64_t n = in->n_rows;
+  std::vector<int64_t> lens(n), off(n + 1, 0);
+  std::vector<uint8_t> notNull(n);
+  if (!gxp::strCatHostLens(cp, src, n, lens.data(), notNull.data())) {
+    ex->err = "a CONCAT / CONCAT_WS output row exceeds 2 GiB";
+    return GX_ERR_INVALID;
+  }
+  for (int64_t i = 0; i < n; i++) off[i + 1] = off[i] + lens[i];
+  if (out->offsets_cap < n + 1 || out->data_cap < off[n]) {
+    ex->err = "output buffer too small";
+    return GX_ERR_INVALID;
+  }
+  gxp::strCatHostEmit(cp, src, n, off.data(), (uint8_t*)out->data);
+  for (int64_t i = 0; i <= n; i++) out->offsets[i] = off[i];
+  if (out->null_bitmap) {
+    std::memset(out->null_bitmap, 0, (n + 7) / 8);
+    for (int64_t i = 0; i < n; i++)
+      if (notNull[i]) out->null_bitmap[i >> 3] |= (uint8_t)(1u << (i & 7));
+  }
+  out->length = (int32_t)n;
+  return GX_OK;
 }
 
 // debug: decimal columns currently served from an int64 units column (fused

@@ -3197,25 +3197,10 @@ __global__ void strWindowKernel(const ProjDesc* __restrict__ dp, int pi) {
         s = gptr<int64_t>(c.offsets)[row];
         len = gptr<int64_t>(c.offsets)[row + 1] - s;
       }
-      // SUBSTR windows compose (builtinSubstring3ArgsSig, byte semantics):
-      // 1-based pos, negative from the end, out-of-range/len<=0 -> empty
-      for (int w = 0; w < sp.nWin; w++) {
-        int64_t pos = sp.winPos[w], L = sp.winLen[w];
-        if (L == -1) {  // TRIM: a both-ends space strip stays a window
-          auto p = gptr<uint8_t>(c.data);
-          while (len > 0 && p[s] == ' ') { s++; len--; }
-          while (len > 0 && p[s + len - 1] == ' ') len--;
-          continue;
-        }
-        int64_t start = pos < 0 ? len + pos + 1 : pos;
-        if (start < 1 || start > len || L <= 0) {
-          len = 0;
-          break;
-        }
-        int64_t l2 = L < len - (start - 1) ? L : len - (start - 1);
-        s += start - 1;
-        len = l2;
-      }
+      // SUBSTR windows compose, TRIM stays a window (gx_strcat.h)
+      auto p = gptr<uint8_t>(c.data);
+      strWindowFold(sp.nWin, sp.winPos, sp.winLen, &s, &len,
+                    [&](int64_t i) { return p[i]; });
     }
     sp.starts[row] = s;
     sp.lens[row] = len;
@@ -3259,6 +3244,183 @@ int gxStrEmit(const ProjDesc* devDesc, const ProjDesc& h, int progIdx,
   hipLaunchKernelGGL(strEmitKernel, dim3(gridFor(h.table.nRows)), dim3(256),
                      0, (hipStream_t)stream, devDesc, progIdx, outOffsets,
                      outData);
+  return (int)hipGetLastError();
+}
+
+// ---- composed string outputs (CONCAT / CONCAT_WS / CAST_STR) ----
+// Both kernels run the piece table and byte mapping of gx_strcat.h. The
+// program, the constant pool and the WINDOW pieces' column data pointers are
+// staged in LDS once per block (as raw bytes: StrCatProg has member
+// initializers, which a __shared__ object may not run).
+struct CatStage {
+  StrCatProg prog;
+  uint8_t pool[kStrCatPoolBytes];
+  const uint8_t* data[kStrCatMaxPieces];
+};
+
+__device__ inline void catStageLoad(CatStage& st, const ProjDesc& d, int ci) {
+  static_assert(sizeof(StrCatProg) % 4 == 0, "copied by words");
+  const uint32_t* src = (const uint32_t*)&d.cat[ci];
+  uint32_t* dst = (uint32_t*)&st.prog;
+  for (int i = threadIdx.x; i < (int)(sizeof(StrCatProg) / 4); i += blockDim.x)
+    dst[i] = src[i];
+  for (int i = threadIdx.x; i < kStrCatPoolBytes; i += blockDim.x)
+    st.pool[i] = d.catPool[i];
+  if (threadIdx.x < kStrCatMaxPieces) {
+    const StrPiece& pc = d.cat[ci].piece[threadIdx.x];
+    bool win = (int)threadIdx.x < d.cat[ci].nPieces && pc.kind == SPK_WINDOW;
+    st.data[threadIdx.x] =
+        win ? (const uint8_t*)d.table.cols[pc.col].data : nullptr;
+  }
+  __syncthreads();
+}
+
+struct CatDevSrc {
+  const ProjDesc& d;
+  const CatStage& st;
+  __device__ bool strNull(int p, int64_t row) const {
+    return colIsNull(d.table.cols[st.prog.piece[p].col], row);
+  }
+  __device__ void strRange(int p, int64_t row, int64_t* s, int64_t* len) const {
+    const DevCol& c = d.table.cols[st.prog.piece[p].col];
+    if (c.denseOffsets) {
+      *s = row;
+      *len = 1;
+    } else {
+      *s = gptr<int64_t>(c.offsets)[row];
+      *len = gptr<int64_t>(c.offsets)[row + 1] - *s;
+    }
+  }
+  __device__ uint8_t strByte(int p, int64_t i) const {
+    return gptr<uint8_t>(st.data[p])[i];
+  }
+  __device__ bool i64At(int p, int64_t row, int64_t* v) const {
+    const StrPiece& pc = st.prog.piece[p];
+    if (pc.col >= 0) {  // a plain int64 column reads the table directly
+      const DevCol& c = d.table.cols[pc.col];
+      if (colIsNull(c, row)) return false;
+      *v = gptr<int64_t>(c.data)[row];
+      return true;
+    }
+    if (gptr<uint8_t>(d.outNotNull[pc.slot])[row] == 0) return false;
+    *v = gptr<int64_t>(d.outData[pc.slot])[row];
+    return true;
+  }
+  __device__ uint8_t pool(int i) const { return st.pool[i]; }
+};
+
+// length pass: one lane per row, 9 B/row out, no per-piece temporaries
+__global__ __launch_bounds__(256) void strCatLensKernel(
+    const ProjDesc* __restrict__ dp, int ci, int64_t* __restrict__ lens,
+    uint8_t* __restrict__ notNull) {
+  __shared__ __align__(16) uint8_t stRaw[sizeof(CatStage)];
+  CatStage& st = *reinterpret_cast<CatStage*>(stRaw);
+  const ProjDesc& d = *dp;
+  catStageLoad(st, d, ci);
+  CatDevSrc src{d, st};
+  int64_t n = d.table.nRows;
+  for (int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; row < n;
+       row += (int64_t)gridDim.x * blockDim.x) {
+    StrCatNoSink sink;
+    uint8_t nn = 0;
+    int64_t len = strCatRow(st.prog, src, row, sink, &nn);
+    if (len < 0) {  // the row drops out of the emit; the engine reports it
+      atomicOr(d.errorFlag, kErrStrRowTooLong);
+      len = 0;
+      nn = 0;
+    }
+    lens[row] = len;
+    notNull[row] = nn;
+  }
+}
+
+// tile piece table in dynamic LDS, piece-major so lanes hit distinct banks:
+// start[nPieces][256] i64, off[257] i64, end[nPieces][256] u32, mask[256] u8
+struct CatTileTab {
+  int64_t* startv;
+  uint32_t* endv;
+  uint8_t* maskv;
+  __device__ int64_t start(int p, int r) const { return startv[p * kStrCatTile + r]; }
+  __device__ int64_t end(int p, int r) const { return endv[p * kStrCatTile + r]; }
+  __device__ uint32_t mask(int r) const { return maskv[r]; }
+};
+struct CatTileSink {
+  const CatTileTab& t;
+  int r;
+  __device__ void put(int p, int64_t s, int64_t e) {
+    t.startv[p * kStrCatTile + r] = s;
+    t.endv[p * kStrCatTile + r] = (uint32_t)e;
+  }
+  __device__ void mask(uint32_t m) { t.maskv[r] = (uint8_t)m; }
+};
+static size_t catTileLdsBytes(int nPieces) {
+  return (size_t)nPieces * kStrCatTile * 12 + (kStrCatTile + 1) * 8 + kStrCatTile;
+}
+
+// emit pass: a block takes 256-row tiles; each lane recomputes its row's
+// piece table into LDS, then all lanes stride over the tile's contiguous
+// output bytes, a dword each, so stores coalesce whatever the row lengths are
+__global__ __launch_bounds__(256) void strCatEmitKernel(
+    const ProjDesc* __restrict__ dp, int ci,
+    const int64_t* __restrict__ outOffsets, uint8_t* __restrict__ outData) {
+  __shared__ __align__(16) uint8_t stRaw[sizeof(CatStage)];
+  CatStage& st = *reinterpret_cast<CatStage*>(stRaw);
+  extern __shared__ __align__(16) uint8_t catLds[];
+  const ProjDesc& d = *dp;
+  catStageLoad(st, d, ci);
+  CatDevSrc src{d, st};
+  const int np = st.prog.nPieces;
+  CatTileTab tab;
+  tab.startv = (int64_t*)catLds;
+  int64_t* off = tab.startv + np * kStrCatTile;
+  tab.endv = (uint32_t*)(off + kStrCatTile + 1);
+  tab.maskv = (uint8_t*)(tab.endv + np * kStrCatTile);
+  const int64_t n = d.table.nRows;
+  const int64_t nTiles = (n + kStrCatTile - 1) / kStrCatTile;
+  const int tid = threadIdx.x;
+  for (int64_t tile = blockIdx.x; tile < nTiles; tile += gridDim.x) {
+    const int64_t r0 = tile * kStrCatTile;
+    const int T = n - r0 < kStrCatTile ? (int)(n - r0) : kStrCatTile;
+    if (tid < T) {
+      CatTileSink sink{tab, tid};
+      uint8_t nn = 0;
+      (void)strCatRow(st.prog, src, r0 + tid, sink, &nn);
+    }
+    for (int i = tid; i <= T; i += blockDim.x) off[i] = outOffsets[r0 + i];
+    __syncthreads();
+    // one aligned output word per lane and step (outData is an allocation
+    // base, so w is a dword address); the tile's ragged ends store bytes
+    const int64_t b0 = off[0], b1 = off[T];
+    for (int64_t w = (b0 & ~(int64_t)3) + 4 * tid; w < b1;
+         w += 4 * (int64_t)blockDim.x) {
+      const int64_t lo = w < b0 ? b0 : w;
+      const int64_t hi = w + 4 < b1 ? w + 4 : b1;
+      uint32_t word = strCatWord(st.prog, src, tab, off, T, w, lo, hi);
+      if (hi - lo == 4) {
+        *(uint32_t*)(outData + w) = word;
+      } else {
+        for (int64_t g = lo; g < hi; g++)
+          outData[g] = (uint8_t)(word >> (8 * (int)(g - w)));
+      }
+    }
+    __syncthreads();
+  }
+}
+
+int gxStrCatLens(const ProjDesc* devDesc, const ProjDesc& h, int catIdx,
+                 int64_t* lens, uint8_t* notNull, void* stream) {
+  if (h.table.nRows == 0) return 0;
+  hipLaunchKernelGGL(strCatLensKernel, dim3(gridFor(h.table.nRows)), dim3(256),
+                     0, (hipStream_t)stream, devDesc, catIdx, lens, notNull);
+  return (int)hipGetLastError();
+}
+
+int gxStrCatEmit(const ProjDesc* devDesc, const ProjDesc& h, int catIdx,
+                 const int64_t* outOffsets, uint8_t* outData, void* stream) {
+  if (h.table.nRows == 0) return 0;
+  hipLaunchKernelGGL(strCatEmitKernel, dim3(gridFor(h.table.nRows)), dim3(256),
+                     catTileLdsBytes(h.cat[catIdx].nPieces),
+                     (hipStream_t)stream, devDesc, catIdx, outOffsets, outData);
   return (int)hipGetLastError();
 }
 

@@ -26,6 +26,10 @@ CUSTOMER_TYPES = [GX_TYPE_I64, GX_TYPE_STRING]
 # general LIKE / NOT LIKE (include/gx_executor.h): args (string column,
 # const pattern [, const i64 escape byte])
 GX_F_LIKE, GX_F_NOT_LIKE = 54, 55
+# composed string outputs of the standalone Projection
+# (include/gx_executor.h): CONCAT(a1, ...), CONCAT_WS(const sep, a1, ...),
+# CAST_STR(int expr)
+GX_F_CONCAT, GX_F_CONCAT_WS, GX_F_CAST_STR = 56, 57, 58
 
 
 def declare_like_helpers(lib):
@@ -39,6 +43,17 @@ def declare_like_helpers(lib):
     lib.gx_like_match.argtypes = [ctypes.c_char_p, ctypes.c_int32,
                                   ctypes.c_int32, ctypes.c_char_p,
                                   ctypes.c_int32]
+    return lib
+
+
+def declare_strcat_helpers(lib):
+    """ctypes signature of the host evaluator of one composed string output
+    (gx_debug_strcat_eval); returns lib."""
+    from tests.gxlib import GxChunk, GxCol
+    lib.gx_debug_strcat_eval.restype = ctypes.c_int32
+    lib.gx_debug_strcat_eval.argtypes = [ctypes.c_void_p, ctypes.c_int32,
+                                         ctypes.POINTER(GxChunk),
+                                         ctypes.POINTER(GxCol)]
     return lib
 
 
