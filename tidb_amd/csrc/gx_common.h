@@ -184,7 +184,8 @@ struct AggDesc {
   int32_t fcol = -1;  // f64 sum/avg: source column (bypasses the integer VM;
                       // the value loads raw through a fetch slot and
                       // accumulates with f64 atomics — oracle/exec.cpp f64
-                      // path, stated-tolerance parity)
+                      // path, stated-tolerance parity). count(f64 column)
+                      // sets it too: its count follows that column's NULLs
 };
 
 constexpr int kMaxAggs = 12;

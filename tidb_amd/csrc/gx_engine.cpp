@@ -2619,7 +2619,9 @@ static int32_t compileFused(gx_exec* ex) {
           srcColF = e.colIdx;
         }
       }
-      if ((ad.func != GX_AGG_SUM && ad.func != GX_AGG_AVG) || srcColF < 0) {
+      // count(f) keeps no sum: it only reads the column's NULL bitmap
+      if ((ad.func != GX_AGG_SUM && ad.func != GX_AGG_AVG &&
+           ad.func != GX_AGG_COUNT) || srcColF < 0) {
         ex->err = "device f64 aggregates support sum/avg over a float column";
         return GX_ERR_INVALID;
       }
@@ -2651,7 +2653,8 @@ static int32_t compileFused(gx_exec* ex) {
   ex->desc.nAccSlots = 0;
   for (int a = 0; a < ex->desc.nAggs; a++) {
     const gxp::AggDesc& ad = ex->desc.aggs[a];
-    if (ad.fcol >= 0) {  // f64 sum/avg: slot keyed by the source column
+    if (ad.fcol >= 0 && ad.func != GX_AGG_COUNT) {
+      // f64 sum/avg: slot keyed by the source column
       int found = -1;
       for (int s = 0; s < ex->desc.nAccSlots; s++)
         if (ex->desc.accKind[s] == 3 && ex->desc.accFcol[s] == ad.fcol) {

@@ -986,6 +986,11 @@ const JitProg* compile(const FusedQueryDesc& d, bool repl,
       if (whyNot) *whyNot = "f64 accumulator not specialized";
       return nullptr;
     }
+  for (int a = 0; a < d.nAggs; a++)
+    if (d.aggs[a].fcol >= 0) {  // count(f64 column): NULLs read off the bitmap
+      if (whyNot) *whyNot = "f64 argument not specialized";
+      return nullptr;
+    }
   for (int i = 0; i < d.nIns; i++)
     if (d.ins[i].op == gxp::VM_STRLEN) {
       if (whyNot) *whyNot = "string builtin not specialized";
