@@ -31,8 +31,13 @@
 #include "gx_common.h"
 #include "gx_decimal.h"
 #include "gx_jit.h"
+#include "gx_result.h"
 
+using gxp::HostCol;
 using gxp::MyDecimal;
+using gxp::OutRowVal;
+using gxp::ResultRow;
+using gxp::decFromUnits;
 
 namespace {
 
@@ -73,15 +78,6 @@ struct PPlan {
   std::vector<PNode> nodes;
 };
 
-// host copy of one bound chunk column
-struct HostCol {
-  int type, frac;
-  std::vector<uint8_t> data;
-  std::vector<uint8_t> nullBitmap;
-  std::vector<int64_t> offsets;
-  int length = 0;
-};
-
 struct Binding {
   bool haveChunks = false;
   std::vector<std::vector<HostCol>> chunks;
@@ -110,16 +106,6 @@ struct JoinPart {
   std::vector<std::vector<int64_t>> colOffsets;  // varlen: n+1 (else empty)
   std::vector<std::vector<uint8_t>> nullBytes;   // byte/row (else empty)
   int64_t n = 0;
-};
-
-struct OutRowVal {
-  bool isNull = false;
-  int type = GX_TYPE_I64;
-  int64_t i64 = 0;
-  uint64_t u64 = 0;
-  double f64 = 0;
-  MyDecimal dec;
-  std::string str;
 };
 
 }  // namespace
@@ -303,13 +289,12 @@ struct gx_exec {
   int aggRoot = -1;  // the HASHAGG node the fused kernel implements
   // DISTINCT rewrite (aggFuncDesc.HasDistinct): the device kernel groups by
   // (orig keys..., arg) — the dedup — and the decode folds back to the orig
-  // keys. distinctNKeys >= 0 marks the rewrite; funcs/fracs are the USER's.
-  std::vector<int> havingConds;  // HAVING: Selection over the agg output,
-                                 // filtered on host over decoded group rows
-  std::vector<int> distinctFuncs;
-  std::vector<int> distinctFracs;
-  std::vector<std::vector<int>> distinctArgSlot;  // per agg: appended-key indices (tuple args have several)
-  int distinctNKeys = -1;
+  // keys. distinct.nKeys >= 0 marks the rewrite; funcs/fracs are the USER's;
+  // argSlot holds appended-key indices (tuple args have several).
+  gxp::DistinctSpec distinct;
+  // HAVING: Selection over the agg output, compiled at build
+  // (compileHaving), filtered on host over the decoded group rows
+  std::vector<gxp::HavingCond> having;
   int sourceNode = -1;
   gxp::FusedQueryDesc desc;
   std::vector<std::pair<int, int>> projRegs;  // projection idx -> (reg, scale)
@@ -356,7 +341,7 @@ struct gx_exec {
   hipStream_t stream = nullptr;
   // results
   bool ranQuery = false;
-  std::vector<std::vector<OutRowVal>> resultRows;
+  std::vector<ResultRow> resultRows;
   size_t emitPos = 0;
   // bare-source emit state
   int64_t srcPos = 0;
@@ -506,65 +491,6 @@ static bool decToUnits(const MyDecimal& d, __int128* out, int* scale) {
   *out = u;
   *scale = d.digitsFrac;
   return true;
-}
-
-// int128 units at `scale` -> canonical MyDecimal (digit-exact value)
-static MyDecimal decFromUnits(__int128 u, int scale) {
-  MyDecimal d;
-  bool neg = u < 0;
-  unsigned __int128 a = neg ? (unsigned __int128)(-u) : (unsigned __int128)u;
-  static const int64_t p10[10] = {1, 10, 100, 1000, 10000, 100000, 1000000,
-                                  10000000, 100000000, 1000000000};
-  // scale may exceed one decimal word (e.g. DecimalDiv results at 18):
-  // compute 10^scale in 128 bits
-  unsigned __int128 pscale = 1;
-  for (int s = scale; s > 0; s -= 9)
-    pscale *= (unsigned)p10[s > 9 ? 9 : s];
-  unsigned __int128 ip = a / pscale;
-  unsigned __int128 fr128 = a % pscale;
-  // integer words, most significant first
-  int32_t words[6] = {0};
-  int nw = 0;
-  if (ip == 0) {
-    words[0] = 0;
-    nw = 1;
-  } else {
-    int32_t tmp[6];
-    int k = 0;
-    while (ip > 0) {
-      tmp[k++] = (int32_t)(ip % 1000000000u);
-      ip /= 1000000000u;
-    }
-    nw = k;
-    for (int i = 0; i < k; i++) words[i] = tmp[k - 1 - i];
-  }
-  int digitsInt = (nw - 1) * 9;
-  {
-    int32_t head = words[0];
-    int hd = 1;
-    while (head >= 10) {
-      head /= 10;
-      hd++;
-    }
-    digitsInt += (words[0] == 0 && nw == 1) ? 1 : hd;
-  }
-  d.digitsInt = (int8_t)digitsInt;
-  d.digitsFrac = (int8_t)scale;
-  d.resultFrac = (int8_t)scale;
-  d.negative = neg && (a != 0);
-  for (int i = 0; i < nw; i++) d.wordBuf[i] = words[i];
-  if (scale > 0) {
-    // frac words, 9 digits each, left-aligned (mydecimal.go word layout):
-    // pad the trailing partial word so the digit count is a word multiple
-    int fw = (scale + 8) / 9;
-    int pad = fw * 9 - scale;
-    unsigned __int128 fadj = fr128 * (unsigned)p10[pad];
-    for (int i = fw - 1; i >= 0; i--) {
-      d.wordBuf[nw + i] = (int32_t)(fadj % 1000000000u);
-      fadj /= 1000000000u;
-    }
-  }
-  return d;
 }
 
 static void setDevColMeta(gxp::DevCol* c, int type, int frac) {
@@ -2099,28 +2025,67 @@ static int32_t compileProject(gx_exec* ex) {
 
 static int32_t compileFused(gx_exec* ex);
 
-// structural validation of HAVING conditions at compile time (the value
-// checks run at decode): leaves are <agg output col cmp const> or
-// IS [NOT] NULL(col), composed with LogicOr; col indexes bound by the
-// aggregate's USER output width
-static bool validHavingCond(gx_exec* ex, int cid, int width) {
-  const PExpr& e = ex->plan.exprs[cid];
+static const char kHavingErr[] =
+    "unsupported HAVING condition (col cmp const, IS NULL, OR of those)";
+
+// append the in-order leaves of one HAVING conjunct: <agg output col cmp
+// const> or IS [NOT] NULL(col), composed with LogicOr; col indexes bound by
+// the aggregate's USER output width
+static bool havingLeaves(const PPlan& plan, int cid, int width,
+                         gxp::HavingCond* out) {
+  const PExpr& e = plan.exprs[cid];
   if (e.kind != EK_CALL) return false;
   if (e.func == GX_F_OR && e.args.size() == 2)
-    return validHavingCond(ex, e.args[0], width) &&
-           validHavingCond(ex, e.args[1], width);
+    return havingLeaves(plan, e.args[0], width, out) &&
+           havingLeaves(plan, e.args[1], width, out);
+  gxp::HavingLeaf leaf;
+  const PExpr* col;
   if ((e.func == GX_F_IS_NULL || e.func == GX_F_IS_NOT_NULL) &&
       e.args.size() == 1) {
-    const PExpr& a0 = ex->plan.exprs[e.args[0]];
-    return a0.kind == EK_COLREF && a0.colIdx >= 0 && a0.colIdx < width;
+    leaf.isNullTest = true;
+    leaf.wantNull = e.func == GX_F_IS_NULL;
+    col = &plan.exprs[e.args[0]];
+  } else {
+    if (e.func < 0 || e.func > GX_F_NE || e.args.size() != 2) return false;
+    col = &plan.exprs[e.args[0]];
+    const PExpr* cst = &plan.exprs[e.args[1]];
+    leaf.cmp = e.func;
+    if (col->kind == EK_CONST && cst->kind == EK_COLREF) {
+      std::swap(col, cst);
+      static const int mirror[6] = {GX_F_GT, GX_F_GE, GX_F_LT, GX_F_LE,
+                                    GX_F_EQ, GX_F_NE};
+      leaf.cmp = mirror[e.func];
+    }
+    if (cst->kind != EK_CONST) return false;
+    leaf.cst.type = cst->retType;
+    leaf.cst.i64 = cst->constI64;
+    leaf.cst.u64 = cst->constTime;
+    leaf.cst.f64 = cst->constF64;
+    leaf.cst.dec = cst->constDec;
+    leaf.cst.str = cst->constStr;
   }
-  if (e.func > GX_F_NE || e.args.size() != 2) return false;
-  const PExpr& l = ex->plan.exprs[e.args[0]];
-  const PExpr& r = ex->plan.exprs[e.args[1]];
-  const PExpr* col = l.kind == EK_COLREF ? &l : &r;
-  const PExpr* cst = l.kind == EK_COLREF ? &r : &l;
-  return col->kind == EK_COLREF && cst->kind == EK_CONST &&
-         col->colIdx >= 0 && col->colIdx < width;
+  if (col->kind != EK_COLREF || col->colIdx < 0 || col->colIdx >= width)
+    return false;
+  leaf.col = col->colIdx;
+  out->push_back(std::move(leaf));
+  return true;
+}
+
+// HAVING shape rules, once, at build: the Selection's conjuncts over the
+// output of aggregate `an` become ex->having. Whether a leaf's value and
+// constant types pair is checked at decode, when the leaf is reached.
+static bool compileHaving(gx_exec* ex, const std::vector<int>& conds,
+                          const PNode& an) {
+  int width = (int)(an.exprs.size() + an.aggFuncs.size());
+  ex->having.clear();
+  for (int cid : conds) {
+    ex->having.emplace_back();
+    if (!havingLeaves(ex->plan, cid, width, &ex->having.back())) {
+      ex->err = kHavingErr;
+      return false;
+    }
+  }
+  return true;
 }
 
 // general aggregation over joined rows: HashAgg <- [Projection] <-
@@ -2182,7 +2147,7 @@ static int32_t compileFused(gx_exec* ex) {
     PNode& aggN = ex->plan.nodes[ex->root];
     bool anyD = false;
     for (int f : aggN.aggFuncs) anyD |= f >= GX_AGG_COUNT_DISTINCT;
-    if (anyD && ex->distinctNKeys < 0) {
+    if (anyD && ex->distinct.nKeys < 0) {
       if (aggN.aggMode != GX_AGG_MODE_COMPLETE) {
         ex->err = "DISTINCT aggregates support COMPLETE mode only";
         return GX_ERR_INVALID;
@@ -2229,10 +2194,10 @@ static int32_t compileFused(gx_exec* ex) {
         }
         slotOf[a].push_back(slotFor(argE));
       }
-      ex->distinctFuncs = aggN.aggFuncs;
-      ex->distinctFracs = aggN.aggFracs;
-      ex->distinctArgSlot = slotOf;
-      ex->distinctNKeys = (int)aggN.exprs.size();
+      ex->distinct.funcs = aggN.aggFuncs;
+      ex->distinct.fracs = aggN.aggFracs;
+      ex->distinct.argSlot = slotOf;
+      ex->distinct.nKeys = (int)aggN.exprs.size();
       for (int e : argExprs) aggN.exprs.push_back(e);
       aggN.aggFuncs.assign(1, GX_AGG_COUNT);
       aggN.aggArgs.assign(1, -1);
@@ -3342,58 +3307,6 @@ static void decodeGroupLane(gx_exec* ex, uint32_t lane, int kind, int type,
   }
 }
 
-// host sort of the (small) fused-agg output for ORDER BY / TopN roots
-static void applyPostSort(gx_exec* ex) {
-  if (!ex->postSort) return;
-
-  {
-    auto cmpVal = [](const OutRowVal& a, const OutRowVal& b) -> int {
-      if (a.isNull || b.isNull) {  // NULL sorts first ascending
-        if (a.isNull && b.isNull) return 0;
-        return a.isNull ? -1 : 1;
-      }
-      switch (a.type) {
-        case GX_TYPE_DECIMAL:
-          return a.dec.Compare(b.dec);
-        case GX_TYPE_TIME: {
-          uint64_t x = a.u64 & ~0xFULL, y = b.u64 & ~0xFULL;
-          return x < y ? -1 : (x > y ? 1 : 0);
-        }
-        case GX_TYPE_STRING: {
-          std::string x = a.str, y = b.str;
-          while (!x.empty() && x.back() == ' ') x.pop_back();
-          while (!y.empty() && y.back() == ' ') y.pop_back();
-          int c = x.compare(y);
-          return c < 0 ? -1 : (c > 0 ? 1 : 0);
-        }
-        case GX_TYPE_F64:
-          return a.f64 < b.f64 ? -1 : (a.f64 > b.f64 ? 1 : 0);
-        default:
-          return a.i64 < b.i64 ? -1 : (a.i64 > b.i64 ? 1 : 0);
-      }
-    };
-    std::stable_sort(ex->resultRows.begin(), ex->resultRows.end(),
-                     [&](const std::vector<OutRowVal>& a,
-                         const std::vector<OutRowVal>& b) {
-                       for (auto& [col, desc] : ex->postSortKeys) {
-                         int c = cmpVal(a[col], b[col]);
-                         if (desc) c = -c;
-                         if (c != 0) return c < 0;
-                       }
-                       return false;
-                     });
-    size_t beginI = std::min<size_t>((size_t)ex->postOffset,
-                                     ex->resultRows.size());
-    size_t endI = ex->postLimit < 0
-                      ? ex->resultRows.size()
-                      : std::min<size_t>(beginI + (size_t)ex->postLimit,
-                                         ex->resultRows.size());
-    std::vector<std::vector<OutRowVal>> sliced(
-        ex->resultRows.begin() + beginI, ex->resultRows.begin() + endI);
-    ex->resultRows = std::move(sliced);
-  }
-}
-
 // a packed group key overflowed its lane (string > 3 bytes or i64 >= 2^31):
 // convert every column to the serialized wide-key path. Returns false when
 // the conversion is impossible (fetch plan full / key store alloc failed).
@@ -3799,9 +3712,10 @@ static int32_t runFused(gx_exec* ex) {
   return fusedDecodeResults(ex);
 }
 
-// download the global table + wide-key records and decode the result
-// rows (shared by the one-shot and the out-of-core streaming paths)
-static int32_t fusedDecodeResults(gx_exec* ex) {
+// occupied group slots of the last fused pass, in key order: the compact
+// block when it answers, else the whole table (it lands in *table)
+static int32_t collectGroupSlots(gx_exec* ex, std::vector<gxp::GroupSlot>* table,
+                                 std::vector<const gxp::GroupSlot*>* occ) {
   const int64_t nSlots1 = (int64_t)1 << ex->desc.globalGroupsLog2;
   // banks beyond 0 are written ONLY by the AOT noLds direct-accumulate
   // path; the LDS flush and the hipRTC kernels land in bank 0 — download
@@ -3810,493 +3724,261 @@ static int32_t fusedDecodeResults(gx_exec* ex) {
   const int usedBanks = ex->desc.noLds ? ex->desc.accBanks : 1;
   // the compact block answers unless it overflowed or the pass skipped it
   // (wide keys); then the whole table comes down as before
-  std::vector<const gxp::GroupSlot*> occ;
   const bool compact =
-      ex->resultCompact && gxp::collectCompactGroups(*ex->hostResult, &occ);
+      ex->resultCompact && gxp::collectCompactGroups(*ex->hostResult, occ);
   ex->lastDecodeCompact = compact;
-  std::vector<gxp::GroupSlot> table;
   if (!compact) {
-    occ.clear();
-    table.resize((size_t)nSlots1 * usedBanks);
-    HIP_OK(ex, hipMemcpy(table.data(), ex->devTable,
-                         table.size() * sizeof(gxp::GroupSlot),
+    occ->clear();
+    table->resize((size_t)nSlots1 * usedBanks);
+    HIP_OK(ex, hipMemcpy(table->data(), ex->devTable,
+                         table->size() * sizeof(gxp::GroupSlot),
                          hipMemcpyDeviceToHost));
     // fold the accumulator banks into bank 0 (gxp::foldGroupSlot, the fold
     // compactGroupsKernel applies on device)
     const int nCnt = ex->desc.sharedCnt ? 1 : ex->desc.nAggs;
     for (int bank = 1; bank < usedBanks; bank++)
       for (int64_t i = 0; i < nSlots1; i++)
-        if (table[i].key != gxp::kEmptyKey)
-          gxp::foldGroupSlot(table[i], table[bank * nSlots1 + i],
+        if ((*table)[i].key != gxp::kEmptyKey)
+          gxp::foldGroupSlot((*table)[i], (*table)[bank * nSlots1 + i],
                              ex->desc.nAccSlots, ex->desc.accKind, nCnt);
-    table.resize((size_t)nSlots1);
-    for (auto& s : table)
-      if (s.key != gxp::kEmptyKey) occ.push_back(&s);
+    table->resize((size_t)nSlots1);
+    for (auto& s : *table)
+      if (s.key != gxp::kEmptyKey) occ->push_back(&s);
   }
   ex->split.lap(5);
   // occupied slots in deterministic order (by key)
-  std::sort(occ.begin(), occ.end(),
+  std::sort(occ->begin(), occ->end(),
             [](const gxp::GroupSlot* a, const gxp::GroupSlot* b) {
               return a->key < b->key;
             });
   if (getenv("GX_DEBUG"))
-    fprintf(stderr, "[gx] occupied group slots: %zu\n", occ.size());
+    fprintf(stderr, "[gx] occupied group slots: %zu\n", occ->size());
+  return GX_OK;
+}
 
-  // wide-key mode: download the key records and decode each occupied slot's
-  // group values; slot keys pack (hash32|recordIdx), so deterministic output
-  // order comes from sorting by the DECODED canonical values instead
-  const bool wideKeys = ex->desc.gkey.wideMode != 0;
-  std::map<const gxp::GroupSlot*, std::vector<OutRowVal>> wideVals;
-  if (wideKeys) {
-    const gxp::GroupKeyDesc& g = ex->desc.gkey;
-    uint64_t nRecs = 0;
-    HIP_OK(ex, hipMemcpy(&nRecs, g.recCursor, 8, hipMemcpyDeviceToHost));
-    if (nRecs > (uint64_t)g.recCap) nRecs = (uint64_t)g.recCap;
-    std::vector<uint8_t> recs((size_t)nRecs * g.recBytes);
-    if (nRecs)
-      HIP_OK(ex, hipMemcpy(recs.data(), g.keyStore, recs.size(),
-                           hipMemcpyDeviceToHost));
-    auto decodeWideCol = [&](const gxp::GroupSlot* s, int k, OutRowVal* v,
-                             std::string* canon) -> int32_t {
-      uint32_t recIdx = (uint32_t)(s->key & 0xFFFFFFFFu);
-      if ((uint64_t)recIdx >= nRecs) {
-        ex->err = "wide key record index out of range";
-        return GX_ERR_INTERNAL;
-      }
-      const uint8_t* rec = recs.data() + (size_t)recIdx * g.recBytes;
-      const uint64_t* r64 = (const uint64_t*)rec;
-      int srcCol = g.col[k];
-      if (srcCol >= 0) v->type = ex->desc.table.cols[srcCol].type;
-      else v->type = srcCol == -2 ? GX_TYPE_I64 : GX_TYPE_DECIMAL;
-      if ((r64[0] >> k) & 1) {
-        v->isNull = true;
-        canon->push_back('\x01');
-        return GX_OK;
-      }
-      canon->push_back('\x02');
-      const uint64_t* f = (const uint64_t*)(rec + 16 + 24 * k);
-      if (g.kind[k] == 3) {
-        v->i64 = (int64_t)f[0];
-        v->u64 = f[0];
-        canon->append((const char*)&f[0], 8);
-      } else if (g.kind[k] == 4) {
-        __int128 units = ((__int128)(int64_t)f[1] << 64) | f[0];
-        if (g.col[k] == -2) {  // computed i64 key (e.g. YEAR(t))
-          v->type = GX_TYPE_I64;
-          v->i64 = (int64_t)units;
-          v->u64 = (uint64_t)v->i64;
-        } else {
-          v->type = GX_TYPE_DECIMAL;
-          v->dec = decFromUnits(units, g.kscale[k]);
-        }
-        canon->append((const char*)&f[0], 16);
-      } else {  // kind 5: trimmed string (prefix inline, tail via owner row)
-        uint64_t len = f[0];
-        v->type = GX_TYPE_STRING;
-        v->str.clear();
-        const char* pfx = (const char*)&f[1];
-        for (uint64_t j = 0; j < len && j < 16; j++) v->str.push_back(pfx[j]);
-        if (len > 16) {
-          int64_t owner = (int64_t)r64[1];
-          const gxp::DevCol& c = ex->desc.table.cols[srcCol];
-          int64_t os = 0;
-          HIP_OK(ex, hipMemcpy(&os, c.offsets + owner, 8, hipMemcpyDeviceToHost));
-          std::vector<uint8_t> tail((size_t)len - 16);
-          HIP_OK(ex, hipMemcpy(tail.data(), (const uint8_t*)c.data + os + 16,
-                               tail.size(), hipMemcpyDeviceToHost));
-          v->str.append((const char*)tail.data(), tail.size());
-        }
-        canon->append((const char*)&len, 8);
-        canon->append(v->str);
-      }
-      return GX_OK;
-    };
-    std::map<const gxp::GroupSlot*, std::string> canonOf;
-    for (const gxp::GroupSlot* s : occ) {
-      std::vector<OutRowVal> vals;
-      std::string ck;
-      for (int k = 0; k < g.nCols; k++) {
-        OutRowVal v;
-        int32_t rc2 = decodeWideCol(s, k, &v, &ck);
-        if (rc2) return rc2;
-        vals.push_back(std::move(v));
-      }
-      canonOf[s] = std::move(ck);
-      wideVals[s] = std::move(vals);
-    }
-    std::sort(occ.begin(), occ.end(),
-              [&](const gxp::GroupSlot* a, const gxp::GroupSlot* b) {
-                return canonOf[a] < canonOf[b];
-              });
+// group column k of one wide-key record -> value, plus its canonical bytes
+static int32_t decodeWideCol(gx_exec* ex, const std::vector<uint8_t>& recs,
+                             uint64_t nRecs, const gxp::GroupSlot* s, int k,
+                             OutRowVal* v, std::string* canon) {
+  const gxp::GroupKeyDesc& g = ex->desc.gkey;
+  uint32_t recIdx = (uint32_t)(s->key & 0xFFFFFFFFu);
+  if ((uint64_t)recIdx >= nRecs) {
+    ex->err = "wide key record index out of range";
+    return GX_ERR_INTERNAL;
   }
+  const uint8_t* rec = recs.data() + (size_t)recIdx * g.recBytes;
+  const uint64_t* r64 = (const uint64_t*)rec;
+  int srcCol = g.col[k];
+  if (srcCol >= 0) v->type = ex->desc.table.cols[srcCol].type;
+  else v->type = srcCol == -2 ? GX_TYPE_I64 : GX_TYPE_DECIMAL;
+  if ((r64[0] >> k) & 1) {
+    v->isNull = true;
+    canon->push_back('\x01');
+    return GX_OK;
+  }
+  canon->push_back('\x02');
+  const uint64_t* f = (const uint64_t*)(rec + 16 + 24 * k);
+  if (g.kind[k] == 3) {
+    v->i64 = (int64_t)f[0];
+    v->u64 = f[0];
+    canon->append((const char*)&f[0], 8);
+  } else if (g.kind[k] == 4) {
+    __int128 units = ((__int128)(int64_t)f[1] << 64) | f[0];
+    if (g.col[k] == -2) {  // computed i64 key (e.g. YEAR(t))
+      v->type = GX_TYPE_I64;
+      v->i64 = (int64_t)units;
+      v->u64 = (uint64_t)v->i64;
+    } else {
+      v->type = GX_TYPE_DECIMAL;
+      v->dec = decFromUnits(units, g.kscale[k]);
+    }
+    canon->append((const char*)&f[0], 16);
+  } else {  // kind 5: trimmed string (prefix inline, tail via owner row)
+    uint64_t len = f[0];
+    v->type = GX_TYPE_STRING;
+    v->str.clear();
+    const char* pfx = (const char*)&f[1];
+    for (uint64_t j = 0; j < len && j < 16; j++) v->str.push_back(pfx[j]);
+    if (len > 16) {
+      int64_t owner = (int64_t)r64[1];
+      const gxp::DevCol& c = ex->desc.table.cols[srcCol];
+      int64_t os = 0;
+      HIP_OK(ex, hipMemcpy(&os, c.offsets + owner, 8, hipMemcpyDeviceToHost));
+      std::vector<uint8_t> tail((size_t)len - 16);
+      HIP_OK(ex, hipMemcpy(tail.data(), (const uint8_t*)c.data + os + 16,
+                           tail.size(), hipMemcpyDeviceToHost));
+      v->str.append((const char*)tail.data(), tail.size());
+    }
+    canon->append((const char*)&len, 8);
+    canon->append(v->str);
+  }
+  return GX_OK;
+}
 
+// wide-key mode: download the key records and decode each occupied slot's
+// group values; slot keys pack (hash32|recordIdx), so deterministic output
+// order comes from sorting by the DECODED canonical values instead
+static int32_t decodeWideKeys(gx_exec* ex,
+                              std::vector<const gxp::GroupSlot*>* occ,
+                              std::map<const gxp::GroupSlot*, ResultRow>* vals) {
+  const gxp::GroupKeyDesc& g = ex->desc.gkey;
+  uint64_t nRecs = 0;
+  HIP_OK(ex, hipMemcpy(&nRecs, g.recCursor, 8, hipMemcpyDeviceToHost));
+  if (nRecs > (uint64_t)g.recCap) nRecs = (uint64_t)g.recCap;
+  std::vector<uint8_t> recs((size_t)nRecs * g.recBytes);
+  if (nRecs)
+    HIP_OK(ex, hipMemcpy(recs.data(), g.keyStore, recs.size(),
+                         hipMemcpyDeviceToHost));
+  std::map<const gxp::GroupSlot*, std::string> canonOf;
+  for (const gxp::GroupSlot* s : *occ) {
+    ResultRow row(g.nCols);
+    std::string ck;
+    for (int k = 0; k < g.nCols; k++) {
+      int32_t rc = decodeWideCol(ex, recs, nRecs, s, k, &row[k], &ck);
+      if (rc) return rc;
+    }
+    canonOf[s] = std::move(ck);
+    (*vals)[s] = std::move(row);
+  }
+  std::sort(occ->begin(), occ->end(),
+            [&](const gxp::GroupSlot* a, const gxp::GroupSlot* b) {
+              return canonOf[a] < canonOf[b];
+            });
+  return GX_OK;
+}
+
+// group column k of a slot: the decoded wide record, else the packed lane
+static OutRowVal groupKeyVal(gx_exec* ex, const gxp::GroupSlot* s, int k,
+                             const ResultRow* wide) {
+  if (wide) return (*wide)[k];
+  OutRowVal v;
+  int srcCol = ex->desc.gkey.col[k];
+  decodeGroupLane(ex, (uint32_t)(s->key >> (32 * k)), ex->desc.gkey.kind[k],
+                  ex->desc.table.cols[srcCol].type, &v);
+  return v;
+}
+
+// one group slot -> one result row (group keys, then every aggregate's
+// final value; PARTIAL mode emits the canonical (state, count) pairs)
+static int32_t slotToRow(gx_exec* ex, const gxp::GroupSlot* s,
+                         const ResultRow* wide, ResultRow* row) {
   const PNode& agg = ex->plan.nodes[ex->aggRoot];
-  bool partial = agg.aggMode == GX_AGG_MODE_PARTIAL;
-  ex->resultRows.clear();
-  // zero-row, no-group-by => one row (count=0, sums NULL)
-  if (occ.empty() && agg.exprs.empty() && !partial) {
-    gxp::GroupSlot zero{};
-    zero.key = 0;
-    std::memset(zero.accLo, 0, sizeof(zero.accLo));
-    std::memset(zero.accHi, 0, sizeof(zero.accHi));
-    std::memset(zero.cnt, 0, sizeof(zero.cnt));
-    static gxp::GroupSlot zslot;
-    zslot = zero;
-    occ.push_back(&zslot);
+  const bool partial = agg.aggMode == GX_AGG_MODE_PARTIAL;
+  for (int k = 0; k < ex->desc.gkey.nCols; k++)
+    row->push_back(groupKeyVal(ex, s, k, wide));
+  for (int a = 0; a < ex->desc.nAggs; a++) {
+    const gxp::AggDesc& ad = ex->desc.aggs[a];
+    int phys = ex->desc.accMap[a];
+    __int128 acc = phys >= 0
+        ? (((__int128)s->accHi[phys] << 64) | s->accLo[phys]) : 0;
+    int64_t cnt = s->cnt[ex->desc.sharedCnt ? 0 : a];
+    if (getenv("GX_DEBUG_DESC") && phys >= 0)
+      fprintf(stderr, "[host] agg%d acc lo=%llu hi=%lld cnt=%lld\n", (int)a,
+              (unsigned long long)s->accLo[phys], (long long)s->accHi[phys],
+              (long long)cnt);
+    OutRowVal v;
+    bool withCount = false;  // a PARTIAL SUM/AVG state is (sum, count)
+    if (ad.fr >= 0) {  // firstrow(group col): decode from the group key
+      v = groupKeyVal(ex, s, ad.fr, wide);
+    } else if (ad.func == GX_AGG_COUNT) {
+      v.type = GX_TYPE_I64;
+      v.i64 = cnt;
+    } else if (phys >= 0 && ex->desc.accKind[phys] == 3) {  // f64 sum/avg
+      double sum;
+      std::memcpy(&sum, &s->accLo[phys], 8);
+      gxp::finalizeF64Agg(partial ? GX_AGG_SUM : ad.func, sum, cnt, &v);
+      withCount = partial;
+    } else if (ad.func == GX_AGG_MIN || ad.func == GX_AGG_MAX) {
+      // biased-u64 extreme (accKind 1/2); NULL when no non-null arg row
+      uint64_t raw = s->accLo[phys];
+      if (ex->desc.accKind[phys] == 2) raw = ~raw;
+      int64_t ext = (int64_t)(raw ^ 0x8000000000000000ULL);
+      // output type follows the argument's type (func_max_min.go keeps the
+      // arg type)
+      int argE = agg.aggArgs[a];
+      int srcType = argE >= 0 ? ex->plan.exprs[argE].retType
+                              : GX_TYPE_DECIMAL;
+      v.type = srcType;
+      if (cnt == 0) {
+        v.isNull = true;
+      } else if (srcType == GX_TYPE_I64) {
+        v.i64 = ext;
+      } else {
+        v.type = GX_TYPE_DECIMAL;
+        v.dec = decFromUnits((__int128)ext, ad.scale);
+      }
+    } else if (partial) {
+      v.type = GX_TYPE_DECIMAL;
+      if (ad.func == GX_AGG_SUM && cnt == 0) v.isNull = true;
+      else v.dec = decFromUnits(acc, ad.scale);
+      withCount = true;
+    } else if (!gxp::finalizeDecimalAgg(ad.func, decFromUnits(acc, ad.scale),
+                                        cnt, agg.aggFracs[a], &v)) {
+      ex->err = "avg finalize failed";
+      return GX_ERR_INTERNAL;
+    }
+    row->push_back(std::move(v));
+    if (withCount) {
+      row->emplace_back();  // an I64 cell
+      row->back().i64 = cnt;
+    }
   }
+  return GX_OK;
+}
+
+// download the group states and decode the result rows (shared by the
+// one-shot and the out-of-core streaming paths)
+static int32_t fusedDecodeResults(gx_exec* ex) {
+  std::vector<gxp::GroupSlot> table;
+  std::vector<const gxp::GroupSlot*> occ;
+  int32_t rc = collectGroupSlots(ex, &table, &occ);
+  if (rc) return rc;
+  std::map<const gxp::GroupSlot*, ResultRow> wideVals;
+  if (ex->desc.gkey.wideMode != 0) {
+    rc = decodeWideKeys(ex, &occ, &wideVals);
+    if (rc) return rc;
+  }
+  const PNode& agg = ex->plan.nodes[ex->aggRoot];
+  ex->resultRows.clear();
+  // zero-row, no-group-by => one row (count=0, sums NULL); occ points at
+  // `zero`, so it is declared here to outlive the loop below
+  gxp::GroupSlot zero{};
+  if (occ.empty() && agg.exprs.empty() &&
+      agg.aggMode != GX_AGG_MODE_PARTIAL)
+    occ.push_back(&zero);
   for (const gxp::GroupSlot* s : occ) {
-    std::vector<OutRowVal> row;
-    for (int k = 0; k < ex->desc.gkey.nCols; k++) {
-      if (wideKeys) {
-        row.push_back(wideVals[s][k]);
-        continue;
-      }
-      OutRowVal v;
-      int srcCol = ex->desc.gkey.col[k];
-      decodeGroupLane(ex, (uint32_t)(s->key >> (32 * k)), ex->desc.gkey.kind[k],
-                      ex->desc.table.cols[srcCol].type, &v);
-      row.push_back(std::move(v));
-    }
-    for (int a = 0; a < ex->desc.nAggs; a++) {
-      const gxp::AggDesc& ad = ex->desc.aggs[a];
-      int phys = ex->desc.accMap[a];
-      __int128 acc = phys >= 0
-          ? (((__int128)s->accHi[phys] << 64) | s->accLo[phys]) : 0;
-      int64_t cnt = s->cnt[ex->desc.sharedCnt ? 0 : a];
-      if (getenv("GX_DEBUG_DESC") && phys >= 0)
-        fprintf(stderr, "[host] agg%d acc lo=%llu hi=%lld cnt=%lld\n", (int)a,
-                (unsigned long long)s->accLo[phys], (long long)s->accHi[phys],
-                (long long)cnt);
-      if (ad.fr >= 0) {  // firstrow(group col): decode from the group key
-        if (wideKeys) {
-          row.push_back(wideVals[s][ad.fr]);
-          continue;
-        }
-        OutRowVal v;
-        int srcCol = ex->desc.gkey.col[ad.fr];
-        decodeGroupLane(ex, (uint32_t)(s->key >> (32 * ad.fr)),
-                        ex->desc.gkey.kind[ad.fr],
-                        ex->desc.table.cols[srcCol].type, &v);
-        row.push_back(std::move(v));
-        continue;
-      }
-      if (ad.func == GX_AGG_COUNT) {
-        OutRowVal v;
-        v.type = GX_TYPE_I64;
-        v.i64 = cnt;
-        row.push_back(std::move(v));
-      } else if (phys >= 0 && ex->desc.accKind[phys] == 3) {  // f64 sum/avg
-        double sum;
-        std::memcpy(&sum, &s->accLo[phys], 8);
-        OutRowVal v;
-        v.type = GX_TYPE_F64;
-        if (cnt == 0) v.isNull = true;
-        else v.f64 = ad.func == GX_AGG_AVG && !partial ? sum / (double)cnt
-                                                       : sum;
-        row.push_back(std::move(v));
-        if (partial) {
-          OutRowVal c2;
-          c2.type = GX_TYPE_I64;
-          c2.i64 = cnt;
-          row.push_back(std::move(c2));
-        }
-      } else if (ad.func == GX_AGG_MIN || ad.func == GX_AGG_MAX) {
-        // biased-u64 extreme (accKind 1/2); NULL when no non-null arg row
-        OutRowVal v;
-        uint64_t raw = s->accLo[phys];
-        if (ex->desc.accKind[phys] == 2) raw = ~raw;
-        int64_t ext = (int64_t)(raw ^ 0x8000000000000000ULL);
-        // output type follows the argument's type (func_max_min.go keeps the
-        // arg type)
-        int argE = agg.aggArgs[a];
-        int srcType = argE >= 0 ? ex->plan.exprs[argE].retType
-                                : GX_TYPE_DECIMAL;
-        v.type = srcType;
-        if (cnt == 0) {
-          v.isNull = true;
-        } else if (srcType == GX_TYPE_I64) {
-          v.i64 = ext;
-        } else {
-          v.type = GX_TYPE_DECIMAL;
-          v.dec = decFromUnits((__int128)ext, ad.scale);
-        }
-        row.push_back(std::move(v));
-      } else if (partial) {
-        OutRowVal v;
-        v.type = GX_TYPE_DECIMAL;
-        if (ad.func == GX_AGG_SUM && cnt == 0) v.isNull = true;
-        else v.dec = decFromUnits(acc, ad.scale);
-        row.push_back(std::move(v));
-        OutRowVal c;
-        c.type = GX_TYPE_I64;
-        c.i64 = cnt;
-        row.push_back(std::move(c));
-      } else if (ad.func == GX_AGG_SUM) {
-        OutRowVal v;
-        v.type = GX_TYPE_DECIMAL;
-        if (cnt == 0) v.isNull = true;
-        else {
-          v.dec = decFromUnits(acc, ad.scale);
-          int aggFrac = agg.aggFracs[a];
-          v.dec.Round(&v.dec, aggFrac, gxp::ModeHalfUp);  // func_sum.go:203-222
-        }
-        row.push_back(std::move(v));
-      } else {  // AVG finalize: DecimalDiv(+4) then Round (func_avg.go:84-109)
-        OutRowVal v;
-        v.type = GX_TYPE_DECIMAL;
-        if (cnt == 0) v.isNull = true;
-        else {
-          MyDecimal sum = decFromUnits(acc, ad.scale);
-          MyDecimal den;
-          den.FromInt(cnt);
-          MyDecimal res;
-          int32_t ec = gxp::DecimalDiv(&sum, &den, &res, gxp::kDivFracIncr);
-          if (ec != gxp::E_OK && ec != gxp::E_TRUNCATED) {
-            ex->err = "avg finalize failed";
-            return GX_ERR_INTERNAL;
-          }
-          int aggFrac = agg.aggFracs[a];
-          res.Round(&res, aggFrac, gxp::ModeHalfUp);
-          v.dec = res;
-        }
-        row.push_back(std::move(v));
-      }
-    }
+    auto w = wideVals.find(s);
+    ResultRow row;
+    rc = slotToRow(ex, s, w == wideVals.end() ? nullptr : &w->second, &row);
+    if (rc) return rc;
     ex->resultRows.push_back(std::move(row));
   }
   ex->split.lap(6);
   ex->split.print();
-  if (ex->distinctNKeys >= 0) {
-    // fold the deduplicated (keys..., args...) rows back to the user's
-    // schema. Inner rows are unique (keys, arg tuple) combinations; a
-    // single arg's values can still repeat across rows (other args
-    // differ), so each agg dedups ITS arg column with a per-group set.
-    const int nk = ex->distinctNKeys;
-    const size_t nA = ex->distinctFuncs.size();
-    auto cmpVal = [](const OutRowVal& a, const OutRowVal& b) -> int {
-      if (a.isNull != b.isNull) return a.isNull ? -1 : 1;
-      if (a.isNull) return 0;
-      switch (a.type) {
-        case GX_TYPE_DECIMAL: return a.dec.Compare(b.dec);
-        case GX_TYPE_STRING:
-          return a.str < b.str ? -1 : (a.str > b.str ? 1 : 0);
-        case GX_TYPE_TIME:
-          return a.u64 < b.u64 ? -1 : (a.u64 > b.u64 ? 1 : 0);
-        case GX_TYPE_F64:
-          return a.f64 < b.f64 ? -1 : (a.f64 > b.f64 ? 1 : 0);
-        default:
-          return a.i64 < b.i64 ? -1 : (a.i64 > b.i64 ? 1 : 0);
-      }
-    };
-    auto tupLess = [&](const std::vector<OutRowVal>& a,
-                       const std::vector<OutRowVal>& b) {
-      for (size_t k = 0; k < a.size() && k < b.size(); k++) {
-        int c = cmpVal(a[k], b[k]);
-        if (c) return c < 0;
-      }
-      return a.size() < b.size();
-    };
-    struct AggAcc {
-      std::set<std::vector<OutRowVal>,
-               std::function<bool(const std::vector<OutRowVal>&,
-                                  const std::vector<OutRowVal>&)>> seen;
-      int64_t cnt = 0;
-      MyDecimal sum;
-    };
-    struct DState {
-      std::vector<OutRowVal> keys;
-      std::vector<AggAcc> accs;
-    };
-    auto keyLess = [&](const std::vector<OutRowVal>* a,
-                       const std::vector<OutRowVal>* b) {
-      for (int k = 0; k < nk; k++) {
-        int c = cmpVal((*a)[k], (*b)[k]);
-        if (c) return c < 0;
-      }
-      return false;
-    };
-    std::map<const std::vector<OutRowVal>*, size_t, decltype(keyLess)> idx(
-        keyLess);
-    std::vector<DState> states;
-    for (auto& r : ex->resultRows) {
-      auto it = idx.find(&r);
-      size_t si;
-      if (it == idx.end()) {
-        DState st;
-        st.keys.assign(r.begin(), r.begin() + nk);
-        for (size_t a = 0; a < nA; a++) {
-          AggAcc acc{std::set<std::vector<OutRowVal>,
-                              std::function<bool(
-                                  const std::vector<OutRowVal>&,
-                                  const std::vector<OutRowVal>&)>>(tupLess)};
-          acc.sum.FromInt(0);
-          st.accs.push_back(std::move(acc));
-        }
-        states.push_back(std::move(st));
-        si = states.size() - 1;
-        idx.emplace(&r, si);
-      } else {
-        si = it->second;
-      }
-      DState& st = states[si];
-      for (size_t a = 0; a < nA; a++) {
-        std::vector<OutRowVal> tup;
-        bool anyNull = false;
-        for (int sl : ex->distinctArgSlot[a]) {
-          const OutRowVal& v = r[nk + sl];
-          anyNull |= v.isNull;
-          tup.push_back(v);
-        }
-        if (anyNull) continue;  // NULL (any element) never counts distinct
-        AggAcc& acc = st.accs[a];
-        if (!acc.seen.insert(tup).second) continue;
-        acc.cnt++;
-        if (tup[0].type == GX_TYPE_DECIMAL &&
-            ex->distinctFuncs[a] != GX_AGG_COUNT_DISTINCT) {
-          MyDecimal tmp;
-          int32_t ec = gxp::DecimalAdd(&acc.sum, &tup[0].dec, &tmp);
-          if (ec != gxp::E_OK && ec != gxp::E_TRUNCATED) {
-            ex->err = "distinct sum overflow";
-            return GX_ERR_INTERNAL;
-          }
-          acc.sum = tmp;
-        }
-      }
-    }
-    if (nk == 0 && states.empty()) {  // scalar default row over zero rows
-      DState st;
-      for (size_t a = 0; a < nA; a++) {
-        AggAcc acc{std::set<std::vector<OutRowVal>,
-                            std::function<bool(
-                                const std::vector<OutRowVal>&,
-                                const std::vector<OutRowVal>&)>>(tupLess)};
-        acc.sum.FromInt(0);
-        st.accs.push_back(std::move(acc));
-      }
-      states.push_back(std::move(st));
-    }
-    idx.clear();  // keys pointed into the OLD resultRows
-    std::vector<std::vector<OutRowVal>> folded;
-    folded.reserve(states.size());
-    for (DState& st : states) {
-      std::vector<OutRowVal> row = st.keys;
-      for (size_t a = 0; a < nA; a++) {
-        AggAcc& acc = st.accs[a];
-        OutRowVal v;
-        if (ex->distinctFuncs[a] == GX_AGG_COUNT_DISTINCT) {
-          v.type = GX_TYPE_I64;
-          v.i64 = acc.cnt;
-        } else if (acc.cnt == 0) {
-          v.type = GX_TYPE_DECIMAL;
-          v.isNull = true;
-        } else if (ex->distinctFuncs[a] == GX_AGG_SUM_DISTINCT) {
-          v.type = GX_TYPE_DECIMAL;
-          v.dec = acc.sum;
-          v.dec.Round(&v.dec, ex->distinctFracs[a], gxp::ModeHalfUp);
-        } else {  // AVG_DISTINCT = sum/count with DivPrecisionIncrement
-          v.type = GX_TYPE_DECIMAL;
-          MyDecimal den, res;
-          den.FromInt(acc.cnt);
-          int32_t ec = gxp::DecimalDiv(&acc.sum, &den, &res, gxp::kDivFracIncr);
-          if (ec != gxp::E_OK && ec != gxp::E_TRUNCATED) {
-            ex->err = "distinct avg division failed";
-            return GX_ERR_INTERNAL;
-          }
-          res.Round(&res, ex->distinctFracs[a], gxp::ModeHalfUp);
-          v.dec = res;
-        }
-        row.push_back(std::move(v));
-      }
-      folded.push_back(std::move(row));
-    }
-    ex->resultRows = std::move(folded);
+  if (ex->distinct.nKeys >= 0) {
+    rc = gxp::foldDistinct(&ex->resultRows, ex->distinct, &ex->err);
+    if (rc) return rc;
   }
-  if (!ex->havingConds.empty()) {
-    // HAVING over the decoded group rows (host; O(#groups)). Leaves:
-    // <output col cmp const>, IS [NOT] NULL, and LogicOr trees of those —
-    // VecEvalBool semantics (NULL rejects within both AND and OR)
-    auto leafPass = [&](const PExpr& e, const std::vector<OutRowVal>& r,
-                        bool* ok) -> bool {
-      if (e.kind == EK_CALL &&
-          (e.func == GX_F_IS_NULL || e.func == GX_F_IS_NOT_NULL) &&
-          e.args.size() == 1) {
-        const PExpr& a0 = ex->plan.exprs[e.args[0]];
-        if (a0.kind != EK_COLREF || a0.colIdx < 0 ||
-            a0.colIdx >= (int)r.size())
-          return *ok = false;
-        return r[a0.colIdx].isNull == (e.func == GX_F_IS_NULL);
-      }
-      if (e.kind != EK_CALL || e.func > GX_F_NE || e.args.size() != 2)
-        return *ok = false;
-      const PExpr* l = &ex->plan.exprs[e.args[0]];
-      const PExpr* rr = &ex->plan.exprs[e.args[1]];
-      int cmp = e.func;
-      if (l->kind == EK_CONST && rr->kind == EK_COLREF) {
-        std::swap(l, rr);
-        static const int mirror[6] = {GX_F_GT, GX_F_GE, GX_F_LT, GX_F_LE,
-                                      GX_F_EQ, GX_F_NE};
-        cmp = mirror[cmp];
-      }
-      if (l->kind != EK_COLREF || rr->kind != EK_CONST || l->colIdx < 0 ||
-          l->colIdx >= (int)r.size())
-        return *ok = false;
-      const OutRowVal& v = r[l->colIdx];
-      if (v.isNull) return false;  // NULL rejects
-      int c;
-      if (v.type == GX_TYPE_DECIMAL && rr->retType == GX_TYPE_DECIMAL) {
-        c = v.dec.Compare(rr->constDec);
-      } else if (v.type == GX_TYPE_I64 && rr->retType == GX_TYPE_I64) {
-        c = v.i64 < rr->constI64 ? -1 : (v.i64 > rr->constI64 ? 1 : 0);
-      } else if (v.type == GX_TYPE_TIME && rr->retType == GX_TYPE_TIME) {
-        uint64_t a = v.u64 & ~0xFULL, b = rr->constTime & ~0xFULL;
-        c = a < b ? -1 : (a > b ? 1 : 0);
-      } else if (v.type == GX_TYPE_STRING &&
-                 rr->retType == GX_TYPE_STRING &&
-                 (cmp == GX_F_EQ || cmp == GX_F_NE)) {
-        std::string a = v.str, b = rr->constStr;  // PAD SPACE
-        while (!a.empty() && a.back() == ' ') a.pop_back();
-        while (!b.empty() && b.back() == ' ') b.pop_back();
-        c = a < b ? -1 : (a > b ? 1 : 0);
-      } else {
-        return *ok = false;
-      }
-      switch (cmp) {
-        case GX_F_LT: return c < 0;
-        case GX_F_LE: return c <= 0;
-        case GX_F_GT: return c > 0;
-        case GX_F_GE: return c >= 0;
-        case GX_F_EQ: return c == 0;
-        default: return c != 0;
-      }
-    };
-    std::function<bool(int, const std::vector<OutRowVal>&, bool*)> condPass =
-        [&](int cid, const std::vector<OutRowVal>& r, bool* ok) -> bool {
-      const PExpr& e = ex->plan.exprs[cid];
-      if (e.kind == EK_CALL && e.func == GX_F_OR && e.args.size() == 2)
-        return condPass(e.args[0], r, ok) || condPass(e.args[1], r, ok);
-      return leafPass(e, r, ok);
-    };
-    bool ok = true;
-    std::vector<std::vector<OutRowVal>> kept;
+  if (!ex->having.empty()) {
+    // HAVING over the decoded group rows (host; O(#groups))
+    std::vector<ResultRow> kept;
     kept.reserve(ex->resultRows.size());
-    for (auto& r : ex->resultRows) {
-      bool pass = true;
-      for (int cid : ex->havingConds) {
-        if (!condPass(cid, r, &ok)) { pass = false; break; }
-      }
-      if (!ok) {
-        ex->err = "unsupported HAVING condition (col cmp const, IS NULL, "
-                  "OR of those)";
+    for (ResultRow& r : ex->resultRows) {
+      bool typeOk = true;
+      bool pass = gxp::havingPass(r, ex->having, &typeOk);
+      if (!typeOk) {
+        ex->err = kHavingErr;
         return GX_ERR_INVALID;
       }
       if (pass) kept.push_back(std::move(r));
     }
     ex->resultRows = std::move(kept);
   }
-  applyPostSort(ex);
+  if (ex->postSort)
+    gxp::sortAndSlice(&ex->resultRows, ex->postSortKeys, ex->postOffset,
+                      ex->postLimit);
   return GX_OK;
 }
-
 
 // ---------------- join-aggregate execution (Q3 class) ----------------
 
@@ -5865,224 +5547,14 @@ static int32_t runFinalHost(gx_exec* ex) {
     ex->err = "FINAL mode needs bound partial chunks";
     return GX_ERR_INVALID;
   }
-  size_t nGroup = agg.exprs.size();
-  struct FState {
-    std::vector<OutRowVal> groupVals;
-    std::vector<MyDecimal> dec;
-    std::vector<int64_t> cnt;
-    std::vector<OutRowVal> val;   // min/max/firstrow merged value
-    std::vector<uint8_t> has;
-    std::vector<double> f64;      // f64 sum partials
-  };
-  // decode one partial cell (min/max/firstrow value columns)
-  auto readCell = [](const HostCol& hc, int i) {
-    OutRowVal v;
-    v.type = hc.type;
-    bool notNull = (hc.nullBitmap[i / 8] >> (i % 8)) & 1;
-    if (!notNull) {
-      v.isNull = true;
-    } else if (hc.type == GX_TYPE_STRING) {
-      int64_t s0 = hc.offsets[i], e0 = hc.offsets[i + 1];
-      v.str.assign((const char*)hc.data.data() + s0, e0 - s0);
-    } else if (hc.type == GX_TYPE_DECIMAL) {
-      std::memcpy(&v.dec, hc.data.data() + i * 40, 40);
-    } else {
-      std::memcpy(&v.u64, hc.data.data() + i * 8, 8);
-      v.i64 = (int64_t)v.u64;
-      std::memcpy(&v.f64, hc.data.data() + i * 8, 8);
-    }
-    return v;
-  };
-  // MergePartialResult compare for extremes (func_max_min.go semantics;
-  // strings: binary collation with PAD SPACE)
-  auto cmpCell = [](const OutRowVal& a, const OutRowVal& b) -> int {
-    switch (a.type) {
-      case GX_TYPE_DECIMAL: return a.dec.Compare(b.dec);
-      case GX_TYPE_F64: return a.f64 < b.f64 ? -1 : (a.f64 > b.f64 ? 1 : 0);
-      case GX_TYPE_TIME: {
-        uint64_t x = a.u64 & ~0xFULL, y = b.u64 & ~0xFULL;
-        return x < y ? -1 : (x > y ? 1 : 0);
-      }
-      case GX_TYPE_STRING: {
-        std::string x = a.str, y = b.str;
-        while (!x.empty() && x.back() == ' ') x.pop_back();
-        while (!y.empty() && y.back() == ' ') y.pop_back();
-        int c = x.compare(y);
-        return c < 0 ? -1 : (c > 0 ? 1 : 0);
-      }
-      default:
-        return a.i64 < b.i64 ? -1 : (a.i64 > b.i64 ? 1 : 0);
-    }
-  };
-  std::map<std::string, FState> groups;
-  std::vector<std::string> order;
-  for (auto& ch : it->second.chunks) {
-    int n = ch.empty() ? 0 : ch[0].length;
-    for (int i = 0; i < n; i++) {
-      // group identity: type-tagged raw values (trimmed strings per
-      // utf8mb4_bin PAD SPACE)
-      std::string key;
-      std::vector<OutRowVal> gvals;
-      for (size_t g = 0; g < nGroup; g++) {
-        const HostCol& hc = ch[g];
-        OutRowVal v;
-        v.type = hc.type;
-        bool notNull = (hc.nullBitmap[i / 8] >> (i % 8)) & 1;
-        if (!notNull) {
-          key.push_back('\0');
-          v.isNull = true;
-        } else if (hc.type == GX_TYPE_STRING) {
-          int64_t s0 = hc.offsets[i], e0 = hc.offsets[i + 1];
-          while (e0 > s0 && hc.data[e0 - 1] == ' ') e0--;
-          v.str.assign((const char*)hc.data.data() + s0, e0 - s0);
-          key.push_back('\1');
-          uint32_t l = (uint32_t)v.str.size();
-          key.append((const char*)&l, 4);
-          key.append(v.str);
-        } else {
-          std::memcpy(&v.u64, hc.data.data() + i * 8, 8);
-          v.i64 = (int64_t)v.u64;
-          key.push_back('\2');
-          key.append((const char*)&v.u64, 8);
-        }
-        gvals.push_back(std::move(v));
-      }
-      auto git = groups.find(key);
-      if (git == groups.end()) {
-        FState st;
-        st.groupVals = std::move(gvals);
-        st.dec.resize(agg.aggFuncs.size());
-        st.cnt.assign(agg.aggFuncs.size(), 0);
-        st.val.resize(agg.aggFuncs.size());
-        st.has.assign(agg.aggFuncs.size(), 0);
-        st.f64.assign(agg.aggFuncs.size(), 0.0);
-        git = groups.emplace(key, std::move(st)).first;
-        order.push_back(key);
-      }
-      FState& st = git->second;
-      size_t col = nGroup;
-      for (size_t a = 0; a < agg.aggFuncs.size(); a++) {
-        int f = agg.aggFuncs[a];
-        if (f == GX_AGG_COUNT) {
-          int64_t c;
-          std::memcpy(&c, ch[col].data.data() + i * 8, 8);
-          st.cnt[a] += c;
-          col += 1;
-        } else if (f == GX_AGG_MIN || f == GX_AGG_MAX) {
-          // extreme of per-shard extremes; NULL partials (all-NULL shard)
-          // are skipped (func_max_min.go merge)
-          OutRowVal v = readCell(ch[col], i);
-          if (!v.isNull) {
-            if (!st.has[a] ||
-                (f == GX_AGG_MAX ? cmpCell(v, st.val[a]) > 0
-                                 : cmpCell(v, st.val[a]) < 0)) {
-              st.val[a] = std::move(v);
-              st.has[a] = 1;
-            }
-          }
-          col += 1;
-        } else if (f == GX_AGG_FIRSTROW) {
-          // first partial row of the group in input order (its value may
-          // legitimately be NULL: the group's first row had a NULL arg)
-          if (!st.has[a]) {
-            st.val[a] = readCell(ch[col], i);
-            st.has[a] = 1;
-          }
-          col += 1;
-        } else if (ch[col].type == GX_TYPE_F64) {  // f64 SUM/AVG partials
-          int64_t c;
-          std::memcpy(&c, ch[col + 1].data.data() + i * 8, 8);
-          if (c > 0) {
-            double v;
-            std::memcpy(&v, ch[col].data.data() + i * 8, 8);
-            st.f64[a] += v;
-            st.cnt[a] += c;
-          }
-          col += 2;
-        } else {  // SUM/AVG: decimal + count
-          int64_t c;
-          std::memcpy(&c, ch[col + 1].data.data() + i * 8, 8);
-          if (c > 0) {
-            MyDecimal v;
-            std::memcpy(&v, ch[col].data.data() + i * 40, 40);
-            MyDecimal tmp;
-            int32_t ec = gxp::DecimalAdd(&st.dec[a], &v, &tmp);
-            if (ec != gxp::E_OK && ec != gxp::E_TRUNCATED) {
-              ex->err = "merge add failed";
-              return GX_ERR_INTERNAL;
-            }
-            st.dec[a] = tmp;
-            st.cnt[a] += c;
-          }
-          col += 2;
-        }
-      }
-    }
-  }
-  ex->resultRows.clear();
-  // zero partial rows, no group-by => the scalar-agg default row
-  // (count=0, sums/extremes NULL — HashAggExec's empty-input semantics)
-  if (nGroup == 0 && order.empty()) {
-    FState st;
-    st.dec.resize(agg.aggFuncs.size());
-    st.cnt.assign(agg.aggFuncs.size(), 0);
-    st.val.resize(agg.aggFuncs.size());
-    st.has.assign(agg.aggFuncs.size(), 0);
-    st.f64.assign(agg.aggFuncs.size(), 0.0);
-    groups.emplace(std::string(), std::move(st));
-    order.push_back(std::string());
-  }
-  for (const std::string& key : order) {
-    FState& st = groups[key];
-    std::vector<OutRowVal> row = st.groupVals;
-    for (size_t a = 0; a < agg.aggFuncs.size(); a++) {
-      int f = agg.aggFuncs[a];
-      OutRowVal v;
-      if (f == GX_AGG_COUNT) {
-        v.type = GX_TYPE_I64;
-        v.i64 = st.cnt[a];
-      } else if (f == GX_AGG_MIN || f == GX_AGG_MAX ||
-                 f == GX_AGG_FIRSTROW) {
-        if (!st.has[a]) {
-          v.isNull = true;
-          v.type = GX_TYPE_DECIMAL;
-        } else {
-          v = st.val[a];
-        }
-      } else if (agg.aggArgs[a] >= 0 &&
-                 ex->plan.exprs[agg.aggArgs[a]].retType == GX_TYPE_F64) {
-        v.type = GX_TYPE_F64;
-        if (st.cnt[a] == 0) v.isNull = true;
-        else v.f64 = f == GX_AGG_AVG ? st.f64[a] / (double)st.cnt[a]
-                                     : st.f64[a];
-      } else if (f == GX_AGG_SUM) {
-        v.type = GX_TYPE_DECIMAL;
-        if (st.cnt[a] == 0) v.isNull = true;
-        else {
-          v.dec = st.dec[a];
-          v.dec.Round(&v.dec, agg.aggFracs[a], gxp::ModeHalfUp);
-        }
-      } else {  // AVG
-        v.type = GX_TYPE_DECIMAL;
-        if (st.cnt[a] == 0) v.isNull = true;
-        else {
-          MyDecimal den;
-          den.FromInt(st.cnt[a]);
-          MyDecimal res;
-          int32_t ec = gxp::DecimalDiv(&st.dec[a], &den, &res, gxp::kDivFracIncr);
-          if (ec != gxp::E_OK && ec != gxp::E_TRUNCATED) {
-            ex->err = "avg finalize failed";
-            return GX_ERR_INTERNAL;
-          }
-          res.Round(&res, agg.aggFracs[a], gxp::ModeHalfUp);
-          v.dec = res;
-        }
-      }
-      row.push_back(std::move(v));
-    }
-    ex->resultRows.push_back(std::move(row));
-  }
-  return GX_OK;
+  gxp::FinalSpec spec;
+  spec.nGroup = agg.exprs.size();
+  spec.funcs = agg.aggFuncs;
+  spec.fracs = agg.aggFracs;
+  for (int argE : agg.aggArgs)
+    spec.argIsF64.push_back(argE >= 0 &&
+                            ex->plan.exprs[argE].retType == GX_TYPE_F64);
+  return gxp::mergeFinal(it->second.chunks, spec, &ex->resultRows, &ex->err);
 }
 
 // ---------------- bare source download (generator parity) ----------------
@@ -6565,76 +6037,6 @@ static int32_t emitSourceChunk(gx_exec* ex, gx_chunk* out, int32_t* rows_out) {
   return emitTableChunk(ex, out, rows_out);
 }
 
-// ---------------- result marshalling ----------------
-
-static int32_t emitResultRows(gx_exec* ex, gx_chunk* out, int32_t* rows_out) {
-  size_t n = std::min<size_t>(ex->resultRows.size() - ex->emitPos, 1024);
-  if (n == 0) {
-    *rows_out = 0;
-    return GX_OK;
-  }
-  std::vector<int64_t> dataPos(out->n_cols, 0);
-  for (int c = 0; c < out->n_cols; c++) {
-    if (out->cols[c].null_bitmap)
-      std::memset(out->cols[c].null_bitmap, 0, ((int)n + 7) / 8);
-    if (out->cols[c].offsets) out->cols[c].offsets[0] = 0;
-  }
-  for (size_t i = 0; i < n; i++) {
-    const std::vector<OutRowVal>& row = ex->resultRows[ex->emitPos + i];
-    if ((int)row.size() != out->n_cols) {
-      ex->err = "output chunk column count mismatch";
-      return GX_ERR_INVALID;
-    }
-    for (int c = 0; c < out->n_cols; c++) {
-      const OutRowVal& v = row[c];
-      gx_col* g = &out->cols[c];
-      bool isStr = g->elem_size == -1 || v.type == GX_TYPE_STRING;
-      if (v.isNull) {
-        if (isStr) g->offsets[i + 1] = g->offsets[i];
-        else {
-          int es = v.type == GX_TYPE_DECIMAL ? 40 : 8;
-          if ((int64_t)(i + 1) * es > g->data_cap) {
-            ex->err = "output buffer too small";
-            return GX_ERR_INVALID;
-          }
-          std::memset((uint8_t*)g->data + i * es, 0, es);
-        }
-        continue;
-      }
-      if (g->null_bitmap) g->null_bitmap[i / 8] |= 1 << (i % 8);
-      if (isStr) {
-        int64_t base = g->offsets[i];
-        if (base + (int64_t)v.str.size() > g->data_cap || (int64_t)i + 1 > g->offsets_cap - 1) {
-          ex->err = "output buffer too small";
-          return GX_ERR_INVALID;
-        }
-        std::memcpy((uint8_t*)g->data + base, v.str.data(), v.str.size());
-        g->offsets[i + 1] = base + v.str.size();
-      } else if (v.type == GX_TYPE_DECIMAL) {
-        if ((int64_t)(i + 1) * 40 > g->data_cap) {
-          ex->err = "output buffer too small";
-          return GX_ERR_INVALID;
-        }
-        std::memcpy((uint8_t*)g->data + i * 40, &v.dec, 40);
-      } else {
-        if ((int64_t)(i + 1) * 8 > g->data_cap) {
-          ex->err = "output buffer too small";
-          return GX_ERR_INVALID;
-        }
-        if (v.type == GX_TYPE_F64)
-          std::memcpy((uint8_t*)g->data + i * 8, &v.f64, 8);
-        else
-          std::memcpy((uint8_t*)g->data + i * 8, &v.i64, 8);
-      }
-    }
-  }
-  for (int c = 0; c < out->n_cols; c++) out->cols[c].length = (int)n;
-  out->n_rows = (int)n;
-  ex->emitPos += n;
-  *rows_out = (int)n;
-  return GX_OK;
-}
-
 // ---------------- C ABI ----------------
 
 // text form of one VM program (gx_debug_vm_program)
@@ -6872,17 +6274,7 @@ gx_exec* gx_build(gx_pb* pb, int32_t root, int32_t device) {
     // HAVING: a Selection over the aggregate's output — run the fused
     // aggregation and filter the (small) decoded group rows on the host
     // (the reference evaluates HAVING the same way, above the agg)
-    ex->havingConds = rn.exprs;
-    {
-      const PNode& an = ex->plan.nodes[rn.child];
-      int width = (int)(an.exprs.size() + an.aggFuncs.size());
-      for (int cid : ex->havingConds)
-        if (!validHavingCond(ex, cid, width)) {
-          ex->err = "unsupported HAVING condition (col cmp const, IS NULL, "
-                    "OR of those)";
-          return ex;
-        }
-    }
+    if (!compileHaving(ex, rn.exprs, ex->plan.nodes[rn.child])) return ex;
     int aggRoot = rn.child;
     int node = aggRoot;
     while (ex->plan.nodes[node].kind == PK_HASHAGG ||
@@ -6924,16 +6316,9 @@ gx_exec* gx_build(gx_pb* pb, int32_t root, int32_t device) {
     // same way — Q1's final Sort, sortexec/sort.go)
     int aggRoot = rn.child;
     if (ex->plan.nodes[aggRoot].kind == PK_SELECTION) {
-      ex->havingConds = ex->plan.nodes[aggRoot].exprs;
+      const std::vector<int>& conds = ex->plan.nodes[aggRoot].exprs;
       aggRoot = ex->plan.nodes[aggRoot].child;
-      const PNode& an = ex->plan.nodes[aggRoot];
-      int width = (int)(an.exprs.size() + an.aggFuncs.size());
-      for (int cid : ex->havingConds)
-        if (!validHavingCond(ex, cid, width)) {
-          ex->err = "unsupported HAVING condition (col cmp const, IS NULL, "
-                    "OR of those)";
-          return ex;
-        }
+      if (!compileHaving(ex, conds, ex->plan.nodes[aggRoot])) return ex;
     }
     int aggWidth = (int)ex->plan.nodes[aggRoot].exprs.size() +
                    (int)ex->plan.nodes[aggRoot].aggFuncs.size();
@@ -7335,7 +6720,7 @@ int32_t gx_next(gx_exec* ex, gx_chunk* out, int32_t* rows_out) {
     }
     ex->ranQuery = true;
   }
-  return emitResultRows(ex, out, rows_out);
+  return gxp::emitRows(ex->resultRows, &ex->emitPos, out, rows_out, &ex->err);
 }
 
 int32_t gx_close(gx_exec* ex) {
