@@ -270,6 +270,14 @@ int32_t gx_pb_streamagg(gx_pb* pb, int32_t child, const int32_t* group_exprs,
                         int32_t n_group, const int32_t* agg_funcs,
                         const int32_t* agg_args, const int32_t* agg_fracs,
                         int32_t n_aggs);
+/* ORDER BY / TopN (sortexec): limit < 0 = full sort. Keys are columns of the
+ * child's output: int64, time, decimal (ordered as int64 units at the
+ * column's frac), f64 (-0.0 ties with 0.0; the order of NaN is unspecified)
+ * and strings of any length (utf8mb4_bin PAD SPACE: trailing spaces
+ * trimmed, unsigned bytes, shorter first, 0x00 is data). NULL sorts first
+ * ascending and last descending. The sorted table may carry varlen columns
+ * as payload. The out-of-core (spilled) sort takes fixed-width and char(1)
+ * columns only. */
 int32_t gx_pb_topn(gx_pb* pb, int32_t child, const int32_t* key_exprs,
                    const uint8_t* key_desc, int32_t n_keys,
                    int64_t limit, int64_t offset);

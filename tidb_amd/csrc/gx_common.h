@@ -12,6 +12,7 @@
 
 #include "gx_like.h"
 #include "gx_strcat.h"
+#include "gx_strkey.h"
 #include "gx_units.h"
 
 namespace gxp {
@@ -752,8 +753,12 @@ int gxDumpDesc(const FusedQueryDesc* devDesc, void* stream);
 struct SortKeyCompose {
   int32_t col;
   int32_t kind;   // 0 = i64 (sign-biased), 1 = time (masked), 2 = dense char,
-                  // 3 = decimal (parsed to int64 units at column frac)
+                  // 3 = decimal (parsed to int64 units at column frac),
+                  // 4 = general varlen string (key = rank[row]; the plan
+                  //     says 2, runDeviceSort builds the rank and sets 4),
+                  // 5 = f64 (f64OrderKey; NaN order unspecified)
   int32_t desc;   // 1 = descending (key complemented)
+  const uint32_t* rank = nullptr;  // kind 4: dense order rank per table row
 };
 // one stable pass: keys[i] = orderKey(table[idx[i]].col); err: sets
 // kErrRetryWide-style flag bit 1 on any unrepresentable decimal key
@@ -773,6 +778,46 @@ int gxSortComposeNullKeys(const uint8_t* bitmap, const uint32_t* idx,
 // gather one column into out (same layout; elemSize 1, 8 or 40)
 int gxSortGatherCol(const void* in, void* out, const uint32_t* idx, int64_t n,
                     int elemSize, void* stream);
+
+// ---- dense rank of a general varlen sort key (gx_strkey.h): MSD refinement
+// over 7-byte window keys, only on the rows still tied. Slot i of a round's
+// active list stands for position act[i] (act == nullptr: round 0, position
+// i holds row i).
+// elen[row] = effective (PAD SPACE trimmed) length, 0 under NULL; *devMax
+// (zeroed by the caller) receives the maximum; a row past 2^32-1 bytes sets
+// kErrStrRowTooLong in *errFlag
+int gxStrKeyElen(const DevCol& col, int64_t n, uint32_t* elen,
+                 uint32_t* devMax, uint32_t* errFlag, void* stream);
+// w[i] = W(row, round), rowAct[i] = row = perm[act[i]], headFlag[i] =
+// head[act[i]]
+int gxStrKeyCompose(const DevCol& col, const uint32_t* elen,
+                    const uint32_t* perm, const uint32_t* act,
+                    const uint32_t* head, int64_t m, uint32_t round,
+                    uint64_t* w, uint32_t* rowAct, uint32_t* headFlag,
+                    void* stream);
+// keys[j] = seg[order[j]]: the segment of the row that stands at slot j
+// after the window sort
+int gxStrKeySegKeys(const uint32_t* seg, const uint32_t* order, uint64_t* keys,
+                    int64_t m, void* stream);
+// write the round's order back: perm[act[j]] = rowAct[order[j]], wSorted[j]
+// = w[order[j]]
+int gxStrKeyPlace(const uint64_t* w, const uint32_t* rowAct,
+                  const uint32_t* order, const uint32_t* act, uint32_t* perm,
+                  uint64_t* wSorted, int64_t m, void* stream);
+// set head[act[j]] on new segment heads; keep[j] = slot stays active
+int gxStrKeyRefine(const uint32_t* seg, const uint64_t* wSorted,
+                   const uint32_t* act, uint32_t* head, uint8_t* keep,
+                   int64_t m, void* stream);
+// rank[perm[pos]] = headScan[pos] - 1 (headScan: inclusive sum of head)
+int gxStrKeyScatterRank(const uint32_t* perm, const uint32_t* headScan,
+                        uint32_t* rank, int64_t n, void* stream);
+int gxInclusiveSumU32(const uint32_t* in, uint32_t* out, int64_t n, void* tmp,
+                      size_t* tmpBytes, void* stream);
+// out = in[j] where keep[j], in order; *devCount = how many. in == nullptr
+// selects from 0, 1, 2, ...
+int gxSelectFlaggedU32(const uint32_t* in, const uint8_t* keep, uint32_t* out,
+                       uint32_t* devCount, int64_t n, void* tmp,
+                       size_t* tmpBytes, void* stream);
 
 // join-agg pipeline steps (gx_kernels.hip)
 int gxJoinAggPhase(int phase, const JoinAggDesc* devDesc, const JoinAggDesc& h,

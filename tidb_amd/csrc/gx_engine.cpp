@@ -2873,7 +2873,11 @@ static int32_t materializeDevice(gx_exec* ex) {
   }
   Binding& b = it->second;
   gxp::DevTable& tab = ex->desc.table;
-  if (b.tpchTable >= 0) {
+  if (b.tpchTable >= 0 && b.tpchTable != GX_TPCH_LINEITEM) {
+    // orders / customer (a general varlen column): the shared generator path
+    int32_t mrc = materializeTable(ex, ex->sourceNode, &tab);
+    if (mrc != GX_OK) return mrc;
+  } else if (b.tpchTable >= 0) {
     tab.nRows = b.tpchRows;
     int64_t n = b.tpchRows;
     for (int c = 0; c < tab.nCols; c++) {
@@ -4421,6 +4425,47 @@ static int32_t gatherColNulls(gx_exec* ex, const gxp::DevCol& src,
   return GX_OK;
 }
 
+// general varlen gather through an index: lengths -> exclusive scan -> byte
+// copy. Fills dst's data, offsets and denseOffsets; the null bitmap is the
+// caller's.
+static int32_t gatherVarlenCol(gx_exec* ex, const gxp::DevCol& src,
+                               const uint32_t* idx, uint64_t total,
+                               gxp::DevCol& dst) {
+  int64_t* lens = (int64_t*)devAlloc(ex, total * 8);
+  dst.offsets = (int64_t*)devAlloc(ex, (total + 1) * 8);
+  if (!lens || !dst.offsets) { ex->err = "hipMalloc failed"; return GX_ERR_INTERNAL; }
+  if (gxp::gxGatherVarlenLens(src.offsets, idx, lens, (int64_t)total,
+                              ex->stream) != 0) {
+    ex->err = "varlen lens launch failed";
+    return GX_ERR_INTERNAL;
+  }
+  size_t tmpBytes = 0;
+  gxp::gxExclusiveSumI64(lens, dst.offsets, (int64_t)total, nullptr,
+                         &tmpBytes, ex->stream);
+  void* tmp = devAlloc(ex, std::max<size_t>(tmpBytes, 1));
+  if (!tmp) { ex->err = "hipMalloc failed"; return GX_ERR_INTERNAL; }
+  HIP_OK(ex, hipMemsetAsync(dst.offsets, 0, 8, ex->stream));
+  if (gxp::gxExclusiveSumI64(lens, dst.offsets, (int64_t)total, tmp,
+                             &tmpBytes, ex->stream) != 0) {
+    ex->err = "varlen offsets scan failed";
+    return GX_ERR_INTERNAL;
+  }
+  int64_t totalBytes = 0;
+  HIP_OK(ex, hipStreamSynchronize(ex->stream));
+  HIP_OK(ex, hipMemcpy(&totalBytes, dst.offsets + total, 8,
+                       hipMemcpyDeviceToHost));
+  dst.data = devAlloc(ex, std::max<int64_t>(totalBytes, 1));
+  if (!dst.data) { ex->err = "hipMalloc failed"; return GX_ERR_INTERNAL; }
+  if (gxp::gxGatherVarlenBytes((const uint8_t*)src.data, src.offsets,
+                               idx, dst.offsets, (uint8_t*)dst.data,
+                               (int64_t)total, ex->stream) != 0) {
+    ex->err = "varlen bytes launch failed";
+    return GX_ERR_INTERNAL;
+  }
+  dst.denseOffsets = 0;
+  return GX_OK;
+}
+
 static int32_t gatherCols(gx_exec* ex, const gxp::DevTable& srcTab,
                           const uint32_t* idx, uint64_t total,
                           gxp::DevTable* out, int dstBase,
@@ -4429,39 +4474,8 @@ static int32_t gatherCols(gx_exec* ex, const gxp::DevTable& srcTab,
     const gxp::DevCol& src = srcTab.cols[c];
     gxp::DevCol& dst = out->cols[dstBase + c];
     if (src.type == GX_TYPE_STRING && !src.denseOffsets) {
-      // general varlen gather: lengths -> exclusive scan -> byte copy
-      int64_t* lens = (int64_t*)devAlloc(ex, total * 8);
-      dst.offsets = (int64_t*)devAlloc(ex, (total + 1) * 8);
-      if (!lens || !dst.offsets) { ex->err = "hipMalloc failed"; return GX_ERR_INTERNAL; }
-      if (gxp::gxGatherVarlenLens(src.offsets, idx, lens, (int64_t)total,
-                                  ex->stream) != 0) {
-        ex->err = "varlen lens launch failed";
-        return GX_ERR_INTERNAL;
-      }
-      size_t tmpBytes = 0;
-      gxp::gxExclusiveSumI64(lens, dst.offsets, (int64_t)total, nullptr,
-                             &tmpBytes, ex->stream);
-      void* tmp = devAlloc(ex, std::max<size_t>(tmpBytes, 1));
-      if (!tmp) { ex->err = "hipMalloc failed"; return GX_ERR_INTERNAL; }
-      HIP_OK(ex, hipMemsetAsync(dst.offsets, 0, 8, ex->stream));
-      if (gxp::gxExclusiveSumI64(lens, dst.offsets, (int64_t)total, tmp,
-                                 &tmpBytes, ex->stream) != 0) {
-        ex->err = "varlen offsets scan failed";
-        return GX_ERR_INTERNAL;
-      }
-      int64_t totalBytes = 0;
-      HIP_OK(ex, hipStreamSynchronize(ex->stream));
-      HIP_OK(ex, hipMemcpy(&totalBytes, dst.offsets + total, 8,
-                           hipMemcpyDeviceToHost));
-      dst.data = devAlloc(ex, std::max<int64_t>(totalBytes, 1));
-      if (!dst.data) { ex->err = "hipMalloc failed"; return GX_ERR_INTERNAL; }
-      if (gxp::gxGatherVarlenBytes((const uint8_t*)src.data, src.offsets,
-                                   idx, dst.offsets, (uint8_t*)dst.data,
-                                   (int64_t)total, ex->stream) != 0) {
-        ex->err = "varlen bytes launch failed";
-        return GX_ERR_INTERNAL;
-      }
-      dst.denseOffsets = 0;
+      int32_t vrc = gatherVarlenCol(ex, src, idx, total, dst);
+      if (vrc) return vrc;
     } else {
       int es = src.type == GX_TYPE_DECIMAL ? 40
                : (src.type == GX_TYPE_STRING ? 1 : 8);
@@ -5559,19 +5573,211 @@ static int32_t runFinalHost(gx_exec* ex) {
 
 // ---------------- bare source download (generator parity) ----------------
 
+// scratch the device sort owns before its LSD chain starts; the string rank
+// build borrows it
+struct SortScratch {
+  uint32_t *idxA, *idxB;
+  uint64_t *keyA, *keyB;
+  uint64_t* devOrAnd;
+  void* tmp;
+  size_t tmpBytes;
+};
+
+// a hipcub temp buffer of at least `need` bytes: the sort's own when it is
+// large enough, else a new allocation that replaces it
+static void* sortTmpFor(gx_exec* ex, SortScratch& sc, size_t need) {
+  if (need > sc.tmpBytes) {
+    void* t = devAlloc(ex, need);
+    if (!t) return nullptr;
+    sc.tmp = t;
+    sc.tmpBytes = need;
+  }
+  return sc.tmp;
+}
+
+// dense order rank of a general varlen column (gx_strkey.h): rank[a] <
+// rank[b] iff row a's string orders before row b's under utf8mb4_bin PAD
+// SPACE, equal iff they compare equal; NULL rows rank with the empty string
+// (the chain's null-bit pass places them). MSD refinement over 7-byte window
+// keys: each round sorts only the rows whose prefix is still shared, inside
+// their tied position ranges. *rankOut stays allocated; the scratch is freed.
+static int32_t buildStringRank(gx_exec* ex, const gxp::DevCol& col, int64_t n,
+                               SortScratch& sc, uint32_t** rankOut) {
+  if (n > 0x7FFFFFFFLL) {
+    ex->err = "string sort key over > 2^31 rows unsupported";
+    return GX_ERR_INVALID;
+  }
+  uint32_t* rank = (uint32_t*)devAlloc(ex, n * 4);
+  if (!rank) { ex->err = "hipMalloc failed (string rank)"; return GX_ERR_INTERNAL; }
+  const size_t mark = ex->devBufs.size();
+  uint32_t* elen = (uint32_t*)devAlloc(ex, n * 4);
+  uint32_t* perm = (uint32_t*)devAlloc(ex, n * 4);
+  uint32_t* head = (uint32_t*)devAlloc(ex, n * 4);
+  uint32_t* rowAct = (uint32_t*)devAlloc(ex, n * 4);
+  uint32_t* seg = (uint32_t*)devAlloc(ex, n * 4);
+  uint32_t* hflag = (uint32_t*)devAlloc(ex, n * 4);
+  uint32_t* iota = (uint32_t*)devAlloc(ex, n * 4);
+  uint32_t* actA = (uint32_t*)devAlloc(ex, n * 4);
+  uint32_t* actB = (uint32_t*)devAlloc(ex, n * 4);
+  uint64_t* wSorted = (uint64_t*)devAlloc(ex, n * 8);
+  uint8_t* keep = (uint8_t*)devAlloc(ex, n);
+  uint32_t* devWord = (uint32_t*)devAlloc(ex, 8);  // [0] max elen / count
+  if (!elen || !perm || !head || !rowAct || !seg || !hflag || !iota || !actA ||
+      !actB || !wSorted || !keep || !devWord) {
+    ex->err = "hipMalloc failed (string rank)";
+    return GX_ERR_INTERNAL;
+  }
+  size_t scanBytes = 0, selBytes = 0;
+  gxp::gxInclusiveSumU32(hflag, seg, n, nullptr, &scanBytes, ex->stream);
+  gxp::gxSelectFlaggedU32(nullptr, keep, actA, devWord, n, nullptr, &selBytes,
+                          ex->stream);
+  if (!sortTmpFor(ex, sc, std::max(scanBytes, selBytes))) {
+    ex->err = "hipMalloc failed (string rank)";
+    return GX_ERR_INTERNAL;
+  }
+  HIP_OK(ex, hipMemsetAsync(devWord, 0, 8, ex->stream));
+  HIP_OK(ex, hipMemsetAsync(head, 0, n * 4, ex->stream));
+  if (gxp::gxSortIota(iota, n, ex->stream) ||
+      gxp::gxStrKeyElen(col, n, elen, devWord, ex->devErr, ex->stream)) {
+    ex->err = "string rank launch failed";
+    return GX_ERR_INTERNAL;
+  }
+  uint32_t hw[2] = {0, 0};
+  HIP_OK(ex, hipMemcpyAsync(hw, devWord, 4, hipMemcpyDeviceToHost, ex->stream));
+  HIP_OK(ex, hipMemcpyAsync(hw + 1, ex->devErr, 4, hipMemcpyDeviceToHost,
+                            ex->stream));
+  HIP_OK(ex, hipStreamSynchronize(ex->stream));
+  if (hw[1] & 512u) {  // kErrStrRowTooLong
+    ex->err = "string sort key longer than 2^32-1 bytes";
+    return GX_ERR_INVALID;
+  }
+  // the loop is bounded on the host: a row is active in round r > 0 only if
+  // its effective length reaches 7r
+  const uint32_t maxRounds = gxp::strKeyMaxRounds(hw[0]);
+  const uint32_t* act = nullptr;  // round 0: position i, row i
+  uint32_t* actNext = actA;
+  int64_t m = n;
+  uint32_t round = 0;
+  while (m > 0) {
+    if (round >= maxRounds) {
+      ex->err = "internal: string rank refinement ran past its round bound";
+      return GX_ERR_INTERNAL;
+    }
+    uint64_t* w = sc.keyA;
+    if (gxp::gxStrKeyCompose(col, elen, perm, act, head, m, round, w, rowAct,
+                             hflag, ex->stream) ||
+        gxp::gxSortKeyBits(w, m, sc.devOrAnd, ex->stream)) {
+      ex->err = "string rank launch failed";
+      return GX_ERR_INTERNAL;
+    }
+    size_t tb = sc.tmpBytes;
+    if (gxp::gxInclusiveSumU32(hflag, seg, m, sc.tmp, &tb, ex->stream)) {
+      ex->err = "string rank segment scan failed";
+      return GX_ERR_INTERNAL;
+    }
+    uint64_t oa[2];
+    uint32_t nSeg = 0;
+    HIP_OK(ex, hipMemcpyAsync(oa, sc.devOrAnd, 16, hipMemcpyDeviceToHost,
+                              ex->stream));
+    HIP_OK(ex, hipMemcpyAsync(&nSeg, seg + (m - 1), 4, hipMemcpyDeviceToHost,
+                              ex->stream));
+    HIP_OK(ex, hipStreamSynchronize(ex->stream));
+    // order[j] = the active slot whose row stands at slot j afterwards
+    const uint32_t* order = nullptr;
+    uint64_t diff = oa[0] ^ oa[1];
+    if (diff != 0) {
+      int beginBit = __builtin_ctzll(diff);
+      int endBit = 64 - __builtin_clzll(diff);
+      if (endBit == 64) beginBit = 0;  // rocPRIM mask overflow, see below
+      size_t need = 0;
+      gxp::gxSortPairs(w, sc.keyB, iota, sc.idxA, m, nullptr, &need, beginBit,
+                       endBit, ex->stream);
+      if (!sortTmpFor(ex, sc, need)) {
+        ex->err = "hipMalloc failed (string rank)";
+        return GX_ERR_INTERNAL;
+      }
+      size_t tb1 = sc.tmpBytes;
+      if (gxp::gxSortPairs(w, sc.keyB, iota, sc.idxA, m, sc.tmp, &tb1,
+                           beginBit, endBit, ex->stream)) {
+        ex->err = "string rank window sort failed";
+        return GX_ERR_INTERNAL;
+      }
+      order = sc.idxA;
+      if (nSeg > 1) {
+        // stable by segment id (1..nSeg): rows return to their own tied
+        // range, in window order inside it
+        int segEnd = 64 - __builtin_clzll((uint64_t)nSeg);
+        uint64_t* segKeys = sc.keyB;  // the sorted windows are not needed
+        if (gxp::gxStrKeySegKeys(seg, sc.idxA, segKeys, m, ex->stream)) {
+          ex->err = "string rank launch failed";
+          return GX_ERR_INTERNAL;
+        }
+        need = 0;
+        gxp::gxSortPairs(segKeys, wSorted, sc.idxA, sc.idxB, m, nullptr, &need,
+                         0, segEnd, ex->stream);
+        if (!sortTmpFor(ex, sc, need)) {
+          ex->err = "hipMalloc failed (string rank)";
+          return GX_ERR_INTERNAL;
+        }
+        size_t tb2 = sc.tmpBytes;
+        if (gxp::gxSortPairs(segKeys, wSorted, sc.idxA, sc.idxB, m, sc.tmp,
+                             &tb2, 0, segEnd, ex->stream)) {
+          ex->err = "string rank segment sort failed";
+          return GX_ERR_INTERNAL;
+        }
+        order = sc.idxB;
+      }
+    }
+    size_t tb3 = sc.tmpBytes;
+    if (gxp::gxStrKeyPlace(w, rowAct, order, act, perm, wSorted, m,
+                           ex->stream) ||
+        gxp::gxStrKeyRefine(seg, wSorted, act, head, keep, m, ex->stream) ||
+        gxp::gxSelectFlaggedU32(act, keep, actNext, devWord, m, sc.tmp, &tb3,
+                                ex->stream)) {
+      ex->err = "string rank launch failed";
+      return GX_ERR_INTERNAL;
+    }
+    uint32_t kept = 0;
+    HIP_OK(ex, hipMemcpyAsync(&kept, devWord, 4, hipMemcpyDeviceToHost,
+                              ex->stream));
+    HIP_OK(ex, hipStreamSynchronize(ex->stream));
+    if ((int64_t)kept > m) {
+      ex->err = "internal: string rank active set grew";
+      return GX_ERR_INTERNAL;
+    }
+    m = kept;
+    act = actNext;
+    actNext = actNext == actA ? actB : actA;
+    round++;
+  }
+  size_t tb4 = sc.tmpBytes;
+  if (gxp::gxInclusiveSumU32(head, seg, n, sc.tmp, &tb4, ex->stream) ||
+      gxp::gxStrKeyScatterRank(perm, seg, rank, n, ex->stream)) {
+    ex->err = "string rank launch failed";
+    return GX_ERR_INTERNAL;
+  }
+  HIP_OK(ex, hipStreamSynchronize(ex->stream));
+  if (getenv("GX_DEBUG"))
+    fprintf(stderr, "[gx] string rank: %lld rows, max effective length %u, "
+            "%u refinement rounds\n", (long long)n, hw[0], round);
+  // a larger tmp allocated above replaces the sort's own: it stays
+  size_t from = mark;
+  auto tmpAt = std::find(ex->devBufs.begin() + mark, ex->devBufs.end(), sc.tmp);
+  if (tmpAt != ex->devBufs.end()) {
+    std::iter_swap(ex->devBufs.begin() + mark, tmpAt);
+    from = mark + 1;
+  }
+  freeSince(ex, from);
+  *rankOut = rank;
+  return GX_OK;
+}
+
 // run the device radix sort once, replacing the table's column buffers with
 // gathered sorted copies (stable LSD passes, innermost key first)
 static int32_t runDeviceSort(gx_exec* ex) {
   gxp::DevTable& tab = ex->desc.table;
   int64_t n = tab.nRows;
   if (n > 0xFFFFFFFFLL) { ex->err = "sort > 2^32 rows unsupported"; return GX_ERR_INVALID; }
-  for (auto& k : ex->devSortKeys) {
-    gxp::DevCol& c = tab.cols[k.col];
-    if (k.kind == 2 && !c.denseOffsets) {
-      ex->err = "general varlen sort key unsupported this round";
-      return GX_ERR_INVALID;
-    }
-  }
   if (n == 0) { ex->devSorted = true; return GX_OK; }
   if (!ex->devErr) ex->devErr = (uint32_t*)devAllocP(ex, 4);
   if (!ex->devErr) { ex->err = "hipMalloc failed (sort err)"; return GX_ERR_INTERNAL; }
@@ -5593,9 +5799,29 @@ static int32_t runDeviceSort(gx_exec* ex) {
   hipEventCreate(&ev0);
   hipEventCreate(&ev1);
   hipEventRecord(ev0, ex->stream);
+  // a general varlen key becomes a dense rank column once, before the chain
+  // (a dense char(1) key stays kind 2); the same column twice shares a rank
+  std::vector<gxp::SortKeyCompose> sortKeys = ex->devSortKeys;
+  for (size_t j = 0; j < sortKeys.size(); j++) {
+    gxp::SortKeyCompose& k = sortKeys[j];
+    if (k.kind != 2 || tab.cols[k.col].denseOffsets) continue;
+    for (size_t i = 0; i < j && !k.rank; i++)
+      if (sortKeys[i].kind == 4 && sortKeys[i].col == k.col)
+        k.rank = sortKeys[i].rank;
+    if (!k.rank) {
+      SortScratch sc{idxA, idxB, keyA, keyB, devOrAnd, tmp, tmpBytes};
+      uint32_t* rank = nullptr;
+      int32_t rrc = buildStringRank(ex, tab.cols[k.col], n, sc, &rank);
+      if (rrc != GX_OK) return rrc;
+      tmp = sc.tmp;
+      tmpBytes = sc.tmpBytes;
+      k.rank = rank;
+    }
+    k.kind = 4;
+  }
   if (gxp::gxSortIota(idxA, n, ex->stream)) { ex->err = "iota launch failed"; return GX_ERR_INTERNAL; }
-  for (int j = (int)ex->devSortKeys.size() - 1; j >= 0; j--) {
-    if (gxp::gxSortComposeKeys(nullptr, tab, ex->devSortKeys[j], idxA, keyA, n,
+  for (int j = (int)sortKeys.size() - 1; j >= 0; j--) {
+    if (gxp::gxSortComposeKeys(nullptr, tab, sortKeys[j], idxA, keyA, n,
                                ex->devErr, ex->stream)) {
       ex->err = "key compose launch failed";
       return GX_ERR_INTERNAL;
@@ -5632,10 +5858,10 @@ static int32_t runDeviceSort(gx_exec* ex) {
     }
     // nullable key: a 1-bit stable pass ABOVE the value bits (sortexec
     // compare semantics: NULL < any value — first on ASC, last on DESC)
-    const gxp::DevCol& kc = tab.cols[ex->devSortKeys[j].col];
+    const gxp::DevCol& kc = tab.cols[sortKeys[j].col];
     if (kc.hasNulls && kc.nullBitmap) {
       if (gxp::gxSortComposeNullKeys(kc.nullBitmap, idxA, keyA, n,
-                                     ex->devSortKeys[j].desc, ex->stream)) {
+                                     sortKeys[j].desc, ex->stream)) {
         ex->err = "null key compose failed";
         return GX_ERR_INTERNAL;
       }
@@ -5663,9 +5889,10 @@ static int32_t runDeviceSort(gx_exec* ex) {
     if (nc > 16) { ex->err = "sort supports <= 16 columns this round"; return GX_ERR_INVALID; }
     for (int c = 0; c < nc; c++) {
       gxp::DevCol& col = tab.cols[c];
+      // general varlen columns take the two-pass gather below
       if (col.type == GX_TYPE_STRING && !col.denseOffsets) {
-        ex->err = "general varlen column in sorted table unsupported this round";
-        return GX_ERR_INVALID;
+        sizes[c] = 0;
+        continue;
       }
       int es = col.type == GX_TYPE_DECIMAL ? 40
                : (col.type == GX_TYPE_STRING ? 1 : 8);
@@ -5680,8 +5907,9 @@ static int32_t runDeviceSort(gx_exec* ex) {
     // reads stay L2-coherent; concurrent columns evict each other
     int grc = 0;
     for (int c = 0; c < nc; c++)
-      grc |= gxp::gxSortGatherCol(ins[c], outs[c], idxA, n, sizes[c],
-                                  ex->stream);
+      if (sizes[c])
+        grc |= gxp::gxSortGatherCol(ins[c], outs[c], idxA, n, sizes[c],
+                                    ex->stream);
     // null bitmaps ride the same permutation (joined-table sort; generator
     // sources have none)
     for (int c = 0; c < nc; c++) {
@@ -5697,8 +5925,18 @@ static int32_t runDeviceSort(gx_exec* ex) {
       ex->err = "gather launch failed";
       return GX_ERR_INTERNAL;
     }
-    for (int c = 0; c < nc; c++)
-      tab.cols[c].data = outs[c];  // dense-char offsets stay the identity ramp
+    for (int c = 0; c < nc; c++) {
+      gxp::DevCol& col = tab.cols[c];
+      if (sizes[c]) {
+        col.data = outs[c];  // dense-char offsets stay the identity ramp
+        continue;
+      }
+      gxp::DevCol nd = col;
+      int32_t vrc = gatherVarlenCol(ex, col, idxA, (uint64_t)n, nd);
+      if (vrc) return vrc;
+      col.data = nd.data;
+      col.offsets = nd.offsets;
+    }
   }
   hipEventRecord(ev1, ex->stream);
   HIP_OK(ex, hipStreamSynchronize(ex->stream));
@@ -6453,8 +6691,9 @@ gx_exec* gx_build(gx_pb* pb, int32_t root, int32_t device) {
       int t = srcn.colTypes[ke.colIdx];
       if (t == GX_TYPE_I64) k.kind = 0;
       else if (t == GX_TYPE_TIME) k.kind = 1;
-      else if (t == GX_TYPE_STRING) k.kind = 2;  // dense char checked at run
+      else if (t == GX_TYPE_STRING) k.kind = 2;  // dense char, or ranked at run
       else if (t == GX_TYPE_DECIMAL) k.kind = 3;
+      else if (t == GX_TYPE_F64) k.kind = 5;
       else {
         ex->err = "unsupported sort key type this round";
         ok = false;
@@ -6531,8 +6770,9 @@ gx_exec* gx_build(gx_pb* pb, int32_t root, int32_t device) {
       int t = ex->desc.table.cols[ke.colIdx].type;
       if (t == GX_TYPE_I64) k.kind = 0;
       else if (t == GX_TYPE_TIME) k.kind = 1;
-      else if (t == GX_TYPE_STRING) k.kind = 2;  // dense char checked at run
+      else if (t == GX_TYPE_STRING) k.kind = 2;  // dense char, or ranked at run
       else if (t == GX_TYPE_DECIMAL) k.kind = 3;
+      else if (t == GX_TYPE_F64) k.kind = 5;
       else {
         ex->err = "unsupported sort key type this round";
         return ex;

@@ -1926,7 +1926,12 @@ __global__ void sortComposeKeysKernel(DevTable tab, SortKeyCompose k,
       // value there): every NULL composes the key of a zero value, so the
       // stable value pass keeps NULL rows in inner-key order and no error
       // flag can come from them; the null-bit pass then places them
-      key = (k.kind == 1 || k.kind == 2) ? 0 : 0x8000000000000000ULL;
+      key = (k.kind == 1 || k.kind == 2 || k.kind == 4)
+                ? 0 : 0x8000000000000000ULL;
+    } else if (k.kind == 4) {  // general varlen: its dense rank (gx_strkey.h)
+      key = k.rank[row];
+    } else if (k.kind == 5) {  // f64: order-preserving IEEE bits
+      key = f64OrderKey(gptr<uint64_t>(c.data)[row]);
     } else if (k.kind == 0) {  // int64: flip sign bit
       key = gptr<uint64_t>(c.data)[row] ^ 0x8000000000000000ULL;
     } else if (k.kind == 1) {  // packed CoreTime: masked compare order
@@ -3487,6 +3492,197 @@ int gxGatherVarlenBytes(const uint8_t* inData, const int64_t* inOffsets,
                      (hipStream_t)stream, inData, inOffsets, idx, outOffsets,
                      outData, n);
   return (int)hipGetLastError();
+}
+
+// ==================================================================
+// dense rank of a general varlen sort key (gx_strkey.h)
+// ==================================================================
+
+// column bytes by index into the data buffer; byte loads only, so nothing
+// beyond the last byte asked for is touched
+struct StrKeyBytes {
+  const uint8_t* data;
+  __device__ uint8_t operator()(int64_t i) const {
+    return gptr<uint8_t>(data)[i];
+  }
+};
+
+// one pass: effective length per row (0 under NULL, whose bytes stay
+// unread) and the column's maximum
+__global__ void strKeyElenKernel(const uint8_t* __restrict__ data,
+                                 const int64_t* __restrict__ offsets,
+                                 const uint8_t* __restrict__ nullBitmap,
+                                 int64_t n, uint32_t* __restrict__ elen,
+                                 uint32_t* devMax, uint32_t* errFlag) {
+  uint32_t mx = 0;
+  for (int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; row < n;
+       row += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t e = 0;
+    bool isNull =
+        nullBitmap && ((nullBitmap[row >> 3] >> (row & 7)) & 1) == 0;
+    if (!isNull) {
+      int64_t s = offsets[row];
+      int64_t len = strKeyTrimLen(StrKeyBytes{data}, s, offsets[row + 1] - s);
+      if (len > 0xFFFFFFFFLL) {
+        atomicOr(errFlag, kErrStrRowTooLong);
+        len = 0;
+      }
+      e = (uint32_t)len;
+    }
+    elen[row] = e;
+    mx = e > mx ? e : mx;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    uint32_t o = __shfl_down(mx, off, 64);
+    mx = o > mx ? o : mx;
+  }
+  if ((threadIdx.x & 63) == 0 && mx) atomicMax(devMax, mx);
+}
+
+__global__ void strKeyComposeKernel(const uint8_t* __restrict__ data,
+                                    const int64_t* __restrict__ offsets,
+                                    const uint32_t* __restrict__ elen,
+                                    const uint32_t* __restrict__ perm,
+                                    const uint32_t* __restrict__ act,
+                                    const uint32_t* __restrict__ head,
+                                    int64_t m, uint32_t round,
+                                    uint64_t* __restrict__ w,
+                                    uint32_t* __restrict__ rowAct,
+                                    uint32_t* __restrict__ headFlag) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t row, hf;
+    if (act) {
+      uint32_t pos = act[i];
+      row = perm[pos];
+      hf = head[pos];
+    } else {  // round 0: the strings in row order, one segment
+      row = (uint32_t)i;
+      hf = i == 0;
+    }
+    uint32_t e = elen[row];
+    // offsets[row] is read only where a byte follows it
+    uint64_t key = 0;
+    if ((uint64_t)round * kStrKeyWin < e)
+      key = strKeyWindow(StrKeyBytes{data}, offsets[row], e, round);
+    w[i] = key;
+    rowAct[i] = row;
+    headFlag[i] = hf;
+  }
+}
+
+__global__ void strKeySegKeysKernel(const uint32_t* __restrict__ seg,
+                                    const uint32_t* __restrict__ order,
+                                    uint64_t* __restrict__ keys, int64_t m) {
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m;
+       j += (int64_t)gridDim.x * blockDim.x)
+    keys[j] = seg[order[j]];
+}
+
+__global__ void strKeyPlaceKernel(const uint64_t* __restrict__ w,
+                                  const uint32_t* __restrict__ rowAct,
+                                  const uint32_t* __restrict__ order,
+                                  const uint32_t* __restrict__ act,
+                                  uint32_t* __restrict__ perm,
+                                  uint64_t* __restrict__ wSorted, int64_t m) {
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m;
+       j += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t k = order ? order[j] : (uint32_t)j;
+    wSorted[j] = w[k];
+    perm[act ? act[j] : (uint32_t)j] = rowAct[k];
+  }
+}
+
+__global__ void strKeyRefineKernel(const uint32_t* __restrict__ seg,
+                                   const uint64_t* __restrict__ wSorted,
+                                   const uint32_t* __restrict__ act,
+                                   uint32_t* __restrict__ head,
+                                   uint8_t* __restrict__ keep, int64_t m) {
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m;
+       j += (int64_t)gridDim.x * blockDim.x) {
+    if (strKeyIsHead(seg, wSorted, j)) head[act ? act[j] : (uint32_t)j] = 1;
+    keep[j] = strKeyStaysActive(seg, wSorted, j, m) ? 1 : 0;
+  }
+}
+
+__global__ void strKeyScatterRankKernel(const uint32_t* __restrict__ perm,
+                                        const uint32_t* __restrict__ headScan,
+                                        uint32_t* __restrict__ rank,
+                                        int64_t n) {
+  for (int64_t pos = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pos < n;
+       pos += (int64_t)gridDim.x * blockDim.x)
+    rank[perm[pos]] = headScan[pos] - 1;
+}
+
+int gxStrKeyElen(const DevCol& col, int64_t n, uint32_t* elen,
+                 uint32_t* devMax, uint32_t* errFlag, void* stream) {
+  hipLaunchKernelGGL(strKeyElenKernel, dim3(gridFor(n)), dim3(256), 0,
+                     (hipStream_t)stream, (const uint8_t*)col.data,
+                     col.offsets, col.hasNulls ? col.nullBitmap : nullptr, n,
+                     elen, devMax, errFlag);
+  return (int)hipGetLastError();
+}
+
+int gxStrKeyCompose(const DevCol& col, const uint32_t* elen,
+                    const uint32_t* perm, const uint32_t* act,
+                    const uint32_t* head, int64_t m, uint32_t round,
+                    uint64_t* w, uint32_t* rowAct, uint32_t* headFlag,
+                    void* stream) {
+  hipLaunchKernelGGL(strKeyComposeKernel, dim3(gridFor(m)), dim3(256), 0,
+                     (hipStream_t)stream, (const uint8_t*)col.data,
+                     col.offsets, elen, perm, act, head, m, round, w, rowAct,
+                     headFlag);
+  return (int)hipGetLastError();
+}
+
+int gxStrKeySegKeys(const uint32_t* seg, const uint32_t* order, uint64_t* keys,
+                    int64_t m, void* stream) {
+  hipLaunchKernelGGL(strKeySegKeysKernel, dim3(gridFor(m)), dim3(256), 0,
+                     (hipStream_t)stream, seg, order, keys, m);
+  return (int)hipGetLastError();
+}
+
+int gxStrKeyPlace(const uint64_t* w, const uint32_t* rowAct,
+                  const uint32_t* order, const uint32_t* act, uint32_t* perm,
+                  uint64_t* wSorted, int64_t m, void* stream) {
+  hipLaunchKernelGGL(strKeyPlaceKernel, dim3(gridFor(m)), dim3(256), 0,
+                     (hipStream_t)stream, w, rowAct, order, act, perm, wSorted,
+                     m);
+  return (int)hipGetLastError();
+}
+
+int gxStrKeyRefine(const uint32_t* seg, const uint64_t* wSorted,
+                   const uint32_t* act, uint32_t* head, uint8_t* keep,
+                   int64_t m, void* stream) {
+  hipLaunchKernelGGL(strKeyRefineKernel, dim3(gridFor(m)), dim3(256), 0,
+                     (hipStream_t)stream, seg, wSorted, act, head, keep, m);
+  return (int)hipGetLastError();
+}
+
+int gxStrKeyScatterRank(const uint32_t* perm, const uint32_t* headScan,
+                        uint32_t* rank, int64_t n, void* stream) {
+  hipLaunchKernelGGL(strKeyScatterRankKernel, dim3(gridFor(n)), dim3(256), 0,
+                     (hipStream_t)stream, perm, headScan, rank, n);
+  return (int)hipGetLastError();
+}
+
+int gxInclusiveSumU32(const uint32_t* in, uint32_t* out, int64_t n, void* tmp,
+                      size_t* tmpBytes, void* stream) {
+  return (int)hipcub::DeviceScan::InclusiveSum(tmp, *tmpBytes, in, out, (int)n,
+                                               (hipStream_t)stream);
+}
+
+int gxSelectFlaggedU32(const uint32_t* in, const uint8_t* keep, uint32_t* out,
+                       uint32_t* devCount, int64_t n, void* tmp,
+                       size_t* tmpBytes, void* stream) {
+  if (in)
+    return (int)hipcub::DeviceSelect::Flagged(tmp, *tmpBytes, in, keep, out,
+                                              devCount, (int)n,
+                                              (hipStream_t)stream);
+  hipcub::CountingInputIterator<uint32_t> iota(0);
+  return (int)hipcub::DeviceSelect::Flagged(tmp, *tmpBytes, iota, keep, out,
+                                            devCount, (int)n,
+                                            (hipStream_t)stream);
 }
 
 }  // namespace gxp
