@@ -270,6 +270,17 @@ struct gx_pb {
   PPlan plan;
 };
 
+// How an executor runs its plan. FUSED: fused aggregation over one source.
+// AGG_OVER_JOIN: join stages materialize the joined rows, the fused
+// aggregation runs over that table. FINAL_HOST: FINAL-mode merge of partial
+// chunks on the host. BARE_SOURCE: a bound source, optionally device-sorted.
+// JOIN_AGG: the Q3-class join-aggregate pipeline. HASH_JOIN, SELECT, PROJECT:
+// the standalone operators, materialized as a device table.
+enum class ExecKind {
+  NONE, FUSED, AGG_OVER_JOIN, FINAL_HOST, BARE_SOURCE, JOIN_AGG, HASH_JOIN,
+  SELECT, PROJECT
+};
+
 struct gx_exec {
   PPlan plan;
   int root = -1;
@@ -278,14 +289,17 @@ struct gx_exec {
   std::string err;
   bool opened = false;
 
-  // compiled fused query
-  bool isFused = false;
-  bool isFinalHost = false;
-  bool isBareSource = false;
-  bool isJoinAgg = false;
+  // the route that took the plan: set once, by gx_build's router, after the
+  // route's compiler succeeds (NONE = not executable)
+  ExecKind kind = ExecKind::NONE;
+  // FUSED and AGG_OVER_JOIN run the fused aggregation kernel over desc
+  bool usesFusedDesc() const {
+    return kind == ExecKind::FUSED || kind == ExecKind::AGG_OVER_JOIN;
+  }
   // the join-aggregate compile met a value-context LIKE: a plan error, not a
   // reason to fall back to aggregation over materialized joined rows
   bool jaLikeRejected = false;
+  // compiled fused query
   int aggRoot = -1;  // the HASHAGG node the fused kernel implements
   // DISTINCT rewrite (aggFuncDesc.HasDistinct): the device kernel groups by
   // (orig keys..., arg) — the dedup — and the decode folds back to the orig
@@ -398,6 +412,7 @@ struct gx_exec {
   int jaSrcCust = -1, jaSrcOrd = -1, jaSrcLi = -1;
   gxp::JoinAggDesc* devJa = nullptr;
   int jaValueScale = 0;
+  int jaAggFrac = 0;  // the SUM's declared result frac
   // output mapping: for each group column: 0 = probe key, 1 = payload0,
   // 2 = payload1; types of the payload cols
   std::vector<int> jaGroupSrc;
@@ -419,7 +434,6 @@ struct gx_exec {
     bool inputsReady = false;            // sources materialized once
     gxp::DevTable buildTab, probeTab;    // resident side tables
   };
-  bool isHashJoin = false;
   std::vector<JoinStage> joinStages;     // root stage last
   // out-of-core join (hash_join_spill.go analog): both sides hash-partition
   // into host-RAM runs when build+probe+output exceed the HBM budget;
@@ -433,19 +447,16 @@ struct gx_exec {
   uint64_t spillBuildPass = 0, spillBuildNullKeys = 0;
   uint64_t joinSpillMatches = 0;
   gxp::HashJoinDesc* devHj = nullptr;
-  // general aggregation over joined rows: runHashJoin materializes the join
-  // output into desc.table, then the fused aggregation runs over it
-  bool aggOverJoin = false;
+  // AGG_OVER_JOIN: runHashJoin materializes the join output into desc.table,
+  // then the fused aggregation runs over it
   bool fusedBindDone = false;
   // decimal columns currently served from DevCol::units (buildDecUnits):
   // fused table / join-agg probe table
   int decUnitsFused = 0, decUnitsJa = 0;
   int lastRowsPerLane = 0;  // gx_debug_rows_per_lane: 0 before any fused pass
   // standalone Selection (compact survivors of a CNF over one source)
-  bool isSelect = false;
   JoinStage selStage;  // probe side only (srcP); hj.post = the CNF
   // standalone Projection (materialize computed columns on device)
-  bool isProject = false;
   bool projOverSelect = false;
   int projSrcNode = -1;
   gxp::ProjDesc pd;
@@ -497,6 +508,14 @@ static void setDevColMeta(gxp::DevCol* c, int type, int frac) {
   c->type = type;
   c->frac = frac;
   c->elemSize = type == GX_TYPE_DECIMAL ? 40 : (type == GX_TYPE_STRING ? -1 : 8);
+}
+
+// column schema -> table metadata (pointers and row count arrive at run time)
+static void setTableMeta(gxp::DevTable* t, const std::vector<int>& types,
+                         const std::vector<int>& fracs) {
+  t->nCols = (int)types.size();
+  for (size_t c = 0; c < types.size(); c++)
+    setDevColMeta(&t->cols[c], types[c], fracs[c]);
 }
 
 #define HIP_OK(ex, call)                                        \
@@ -1099,11 +1118,13 @@ static bool compileTablePred(gx_exec* ex, const PNode& srcNode, int condId,
 // full-sort (TOPN limit<0) wrappers below joins/aggregates do not change
 // their results -- the merge-join plan shape sorts its inputs on the join
 // keys (merge_join.go); the device pipeline hashes instead, so skip them
-static int skipFullSort(gx_exec* ex, int node) {
-  while (ex->plan.nodes[node].kind == PK_TOPN &&
-         ex->plan.nodes[node].limit < 0)
-    node = ex->plan.nodes[node].child;
+static int skipFullSort(const PPlan& plan, int node) {
+  while (plan.nodes[node].kind == PK_TOPN && plan.nodes[node].limit < 0)
+    node = plan.nodes[node].child;
   return node;
+}
+static int skipFullSort(gx_exec* ex, int node) {
+  return skipFullSort(ex->plan, node);
 }
 
 static int unwrapSource(gx_exec* ex, int node, const PNode** selOut) {
@@ -1123,9 +1144,9 @@ static int unwrapSource(gx_exec* ex, int node, const PNode** selOut) {
 // recognize & compile the join-aggregate (Q3-class) plan:
 // TopN <- HashAgg(sum) <- Projection <- HashJoin(probe=lineitem,
 //   build=HashJoin(build=customer, probe=orders))
-static int32_t compileJoinAgg(gx_exec* ex) {
+static int32_t compileJoinAgg(gx_exec* ex, int topnNode) {
   const PPlan& plan = ex->plan;
-  const PNode& topn = plan.nodes[ex->root];
+  const PNode& topn = plan.nodes[topnNode];
   if (topn.limit <= 0 || topn.limit + topn.offset > 100000) {
     ex->err = "device TopN limit too large";
     return GX_ERR_INVALID;
@@ -1336,7 +1357,7 @@ static int32_t compileJoinAgg(gx_exec* ex) {
   ex->jaSrcCust = srcC;
   ex->jaSrcOrd = srcO;
   ex->jaSrcLi = srcL;
-  ex->isJoinAgg = true;
+  ex->jaAggFrac = agg.aggFracs[0];
   return GX_OK;
 }
 
@@ -1617,10 +1638,7 @@ static int32_t compileHashJoinTree(gx_exec* ex, int node) {
   if (rc) return rc;
   // root stage must be last (bottom-up compile order guarantees it)
   gx_exec::JoinStage& st = ex->joinStages[root];
-  ex->desc.table.nCols = (int)st.types.size();
-  for (size_t c = 0; c < st.types.size(); c++)
-    setDevColMeta(&ex->desc.table.cols[c], st.types[c], st.fracs[c]);
-  ex->isHashJoin = true;
+  setTableMeta(&ex->desc.table, st.types, st.fracs);
   return GX_OK;
 }
 
@@ -1644,10 +1662,7 @@ static int32_t compileSelect(gx_exec* ex, int selNode) {
   st.fracs = srcN.colFracs;
   int32_t rc = compilePostJoinPreds(ex, sel, st.types, st.fracs, 0, st.hj);
   if (rc) return rc;
-  ex->desc.table.nCols = (int)st.types.size();
-  for (size_t c = 0; c < st.types.size(); c++)
-    setDevColMeta(&ex->desc.table.cols[c], st.types[c], st.fracs[c]);
-  ex->isSelect = true;
+  setTableMeta(&ex->desc.table, st.types, st.fracs);
   return GX_OK;
 }
 
@@ -1904,9 +1919,9 @@ static bool compileStrCat(gx_exec* ex, ExprBuilder& B, gxp::ProjDesc& pd,
 // (ProjectionExec, projection.go:77): computed expressions materialize as
 // device columns (decimal encode on device), passthrough colrefs alias the
 // input buffers
-static int32_t compileProject(gx_exec* ex) {
+static int32_t compileProject(gx_exec* ex, int projNode) {
   const PPlan& plan = ex->plan;
-  const PNode& pj = plan.nodes[ex->root];
+  const PNode& pj = plan.nodes[projNode];
   int childNode = skipFullSort(ex, pj.child);
   const PNode* cn = &plan.nodes[childNode];
   const std::vector<int>* childTypes;
@@ -1915,7 +1930,6 @@ static int32_t compileProject(gx_exec* ex) {
       plan.nodes[skipFullSort(ex, cn->child)].kind == PK_SOURCE) {
     int32_t rc = compileSelect(ex, childNode);
     if (rc) return rc;
-    ex->isSelect = false;  // dispatched through isProject
     ex->projOverSelect = true;
     childTypes = &ex->selStage.types;
     childFracs = &ex->selStage.fracs;
@@ -2015,15 +2029,11 @@ static int32_t compileProject(gx_exec* ex) {
   // pipeline, no reorder)
   if (finishVmProgram(ex, B, 0) < 0) return GX_ERR_INVALID;
   // OUTPUT schema for emission
-  ex->desc.table.nCols = (int)ex->projOutTypes.size();
-  for (size_t c = 0; c < ex->projOutTypes.size(); c++)
-    setDevColMeta(&ex->desc.table.cols[c], ex->projOutTypes[c],
-                  ex->projOutFracs[c]);
-  ex->isProject = true;
+  setTableMeta(&ex->desc.table, ex->projOutTypes, ex->projOutFracs);
   return GX_OK;
 }
 
-static int32_t compileFused(gx_exec* ex);
+static int32_t compileFused(gx_exec* ex, int aggNode);
 
 static const char kHavingErr[] =
     "unsupported HAVING condition (col cmp const, IS NULL, OR of those)";
@@ -2110,8 +2120,6 @@ static int32_t compileAggOverJoin(gx_exec* ex, int aggNode) {
   }
   int32_t rc = compileHashJoinTree(ex, node);
   if (rc) return rc;
-  ex->isHashJoin = false;  // dispatched through aggOverJoin instead
-  ex->aggOverJoin = true;
   // pseudo source carrying the join output schema (root stage)
   PNode ps;
   ps.kind = PK_SOURCE;
@@ -2127,27 +2135,22 @@ static int32_t compileAggOverJoin(gx_exec* ex, int aggNode) {
     plan.nodes.push_back(copy);
     cur = (int)plan.nodes.size() - 1;
   }
-  int saved = ex->root;
-  ex->root = cur;
-  rc = compileFused(ex);
-  ex->root = saved;
-  if (rc != GX_OK) return rc;
-  // the fused desc's table metadata was overwritten from the pseudo source;
+  // the fused desc's table metadata is overwritten from the pseudo source;
   // actual column pointers/nRows arrive when runHashJoin materializes
-  return GX_OK;
+  return compileFused(ex, cur);
 }
 
 // compile the fused Source->[Selection]->[Projection]->HashAgg pipeline
-static int32_t compileFused(gx_exec* ex) {
+static int32_t compileFused(gx_exec* ex, int aggNode) {
   // DISTINCT rewrite: aggregate over DISTINCT values == group by
   // (keys..., arg) on the device (the dedup falls out of the group table),
   // then fold on the host at decode. All aggs must be DISTINCT over ONE
   // shared arg this round; the inner device agg becomes count(*) (unused).
   {
-    PNode& aggN = ex->plan.nodes[ex->root];
+    PNode& aggN = ex->plan.nodes[aggNode];
     bool anyD = false;
     for (int f : aggN.aggFuncs) anyD |= f >= GX_AGG_COUNT_DISTINCT;
-    if (anyD && ex->distinct.nKeys < 0) {
+    if (anyD) {
       if (aggN.aggMode != GX_AGG_MODE_COMPLETE) {
         ex->err = "DISTINCT aggregates support COMPLETE mode only";
         return GX_ERR_INVALID;
@@ -2205,8 +2208,8 @@ static int32_t compileFused(gx_exec* ex) {
     }
   }
   const PPlan& plan = ex->plan;
-  ex->aggRoot = ex->root;
-  const PNode* agg = &plan.nodes[ex->root];
+  ex->aggRoot = aggNode;
+  const PNode* agg = &plan.nodes[aggNode];
   const PNode* proj = nullptr;
   const PNode* sel = nullptr;
   const PNode* src = nullptr;
@@ -2232,9 +2235,7 @@ static int32_t compileFused(gx_exec* ex) {
     ex->err = "too many source columns";
     return GX_ERR_INVALID;
   }
-  ex->desc.table.nCols = (int)src->colTypes.size();
-  for (size_t c = 0; c < src->colTypes.size(); c++)
-    setDevColMeta(&ex->desc.table.cols[c], src->colTypes[c], src->colFracs[c]);
+  setTableMeta(&ex->desc.table, src->colTypes, src->colFracs);
 
   // selection -> PredDescs (CNF of OR groups: each conjunct may be a
   // LogicOr tree of simple predicates, flattened with orWith group heads)
@@ -2695,7 +2696,6 @@ static int32_t compileFused(gx_exec* ex) {
     else d.rbatch = 2;
     if (getenv("GX_RBATCH")) d.rbatch = atoi(getenv("GX_RBATCH"));
   }
-  ex->isFused = true;
   return GX_OK;
 }
 
@@ -2775,9 +2775,7 @@ static int32_t uploadBoundChunks(gx_exec* ex, Binding& b, gxp::DevTable& tab) {
 // materialize one source (tpch generator or bound chunks) into a device table
 static int32_t materializeTable(gx_exec* ex, int srcNodeId, gxp::DevTable* tab) {
   const PNode& srcNode = ex->plan.nodes[srcNodeId];
-  tab->nCols = (int)srcNode.colTypes.size();
-  for (size_t c = 0; c < srcNode.colTypes.size(); c++)
-    setDevColMeta(&tab->cols[c], srcNode.colTypes[c], srcNode.colFracs[c]);
+  setTableMeta(tab, srcNode.colTypes, srcNode.colFracs);
   auto it = ex->bindings.find(srcNodeId);
   if (it == ex->bindings.end()) {
     ex->err = "source not bound";
@@ -3275,7 +3273,8 @@ static int32_t finalizeFusedBind(gx_exec* ex) {
   // (the conversion would be a new pass each time), and the opt-in glds
   // variant stages the 40 B form.
   ex->decUnitsFused = 0;
-  if (!ex->aggOverJoin && !ex->fusedStreamed && !ex->desc.useGlds) {
+  if (ex->kind != ExecKind::AGG_OVER_JOIN && !ex->fusedStreamed &&
+      !ex->desc.useGlds) {
     gxp::FusedQueryDesc& d = ex->desc;
     std::vector<int> cols;
     for (int f = 0; f < d.nFetch; f++)
@@ -3577,8 +3576,8 @@ static int32_t runFused(gx_exec* ex) {
   if (getenv("GX_FORCE_WIDE")) ex->desc.wide = 1;
   // out-of-core aggregation: a generator source above the HBM budget
   // streams in row-range slices instead of materializing whole
-  if ((!ex->deviceReady || ex->fusedStreamed) && !ex->aggOverJoin &&
-      ex->sourceNode >= 0) {
+  if ((!ex->deviceReady || ex->fusedStreamed) &&
+      ex->kind != ExecKind::AGG_OVER_JOIN && ex->sourceNode >= 0) {
     auto itb = ex->bindings.find(ex->sourceNode);
     if (itb != ex->bindings.end() && !itb->second.haveChunks &&
         itb->second.tpchTable >= 0) {
@@ -4390,8 +4389,7 @@ static int32_t runJoinAgg(gx_exec* ex) {
     v.type = GX_TYPE_DECIMAL;
     __int128 acc = ((__int128)c.accHi << 64) | c.accLo;
     v.dec = decFromUnits(acc, ex->jaValueScale);
-    int aggFrac = ex->plan.nodes[ex->plan.nodes[ex->root].child].aggFracs[0];
-    v.dec.Round(&v.dec, aggFrac, gxp::ModeHalfUp);
+    v.dec.Round(&v.dec, ex->jaAggFrac, gxp::ModeHalfUp);
     row.push_back(std::move(v));
     ex->resultRows.push_back(std::move(row));
   }
@@ -4709,10 +4707,8 @@ static int32_t runJoinStage(gx_exec* ex, gx_exec::JoinStage& st, bool isRoot) {
     return GX_ERR_INVALID;
   }
   // output table (schema fixed at compile; buffers per run)
-  st.out.nCols = (int)st.types.size();
+  setTableMeta(&st.out, st.types, st.fracs);
   st.out.nRows = 0;
-  for (size_t c = 0; c < st.types.size(); c++)
-    setDevColMeta(&st.out.cols[c], st.types[c], st.fracs[c]);
   if (total > 0) {
     hj.outBuild = (uint32_t*)devAlloc(ex, total * 4);
     hj.outProbe = (uint32_t*)devAlloc(ex, total * 4);
@@ -5115,7 +5111,7 @@ static int32_t runHashJoin(gx_exec* ex) {
   // (GX_HBM_BUDGET overrides the free-memory estimate), hash-partition both
   // sides to host RAM and join partition-wise (hash_join_spill.go analog).
   // Single-stage source-fed joins only; partitions persist across re-opens.
-  if (ex->joinStages.size() == 1 && !ex->aggOverJoin &&
+  if (ex->joinStages.size() == 1 && ex->kind != ExecKind::AGG_OVER_JOIN &&
       ex->joinStages[0].srcB >= 0 && ex->joinStages[0].srcP >= 0) {
     gx_exec::JoinStage& st0 = ex->joinStages[0];
     if (!st0.hj.counters) {
@@ -5237,10 +5233,8 @@ static int32_t runSelect(gx_exec* ex) {
   HIP_OK(ex, hipStreamSynchronize(ex->stream));
   uint64_t total = 0;
   HIP_OK(ex, hipMemcpy(&total, hj.counters, 8, hipMemcpyDeviceToHost));
-  st.out.nCols = (int)st.types.size();
+  setTableMeta(&st.out, st.types, st.fracs);
   st.out.nRows = 0;
-  for (size_t c = 0; c < st.types.size(); c++)
-    setDevColMeta(&st.out.cols[c], st.types[c], st.fracs[c]);
   if (total > 0) {
     hj.outProbe = (uint32_t*)devAlloc(ex, total * 4);
     if (!hj.outProbe) { ex->err = "hipMalloc failed"; return GX_ERR_INTERNAL; }
@@ -6486,302 +6480,296 @@ int32_t gx_pb_hashjoin(gx_pb* pb, int32_t build_child, int32_t probe_child,
   return addNode(pb, std::move(n));
 }
 
+// ---------------- plan routing ----------------
+// gx_build peels the root of the plan into a PlanShape (classifyPlan), reads
+// the route or ordered route list off it (routesFor) and compiles each route
+// on a fresh executor over a pristine copy of the plan (compileRoute): the
+// first success is the executor, and no attempt sees what another one did.
+
+// [TopN] <- [HAVING] <- [HashAgg] <- ..., peeled. The only place these shape
+// predicates live.
+struct PlanShape {
+  int topn = -1;    // the root, when it is a TopN / sort
+  int body = -1;    // the node under it (the root itself when there is none)
+  int having = -1;  // body, when it is a Selection over a non-FINAL HashAgg
+  int agg = -1;     // that HashAgg, or body when it is a non-FINAL HashAgg
+  // first node from body down that is no HashAgg, Projection or Selection
+  int bottom = -1;
+};
+
+static PlanShape classifyPlan(const PPlan& plan, int root) {
+  auto fusableAgg = [&](int n) {
+    return plan.nodes[n].kind == PK_HASHAGG &&
+           plan.nodes[n].aggMode != GX_AGG_MODE_FINAL;
+  };
+  PlanShape sh;
+  sh.body = root;
+  if (plan.nodes[root].kind == PK_TOPN) {
+    sh.topn = root;
+    sh.body = plan.nodes[root].child;
+  }
+  if (fusableAgg(sh.body)) {
+    sh.agg = sh.body;
+  } else if (plan.nodes[sh.body].kind == PK_SELECTION &&
+             fusableAgg(plan.nodes[sh.body].child)) {
+    sh.having = sh.body;
+    sh.agg = plan.nodes[sh.body].child;
+  }
+  sh.bottom = sh.body;
+  while (plan.nodes[sh.bottom].kind == PK_HASHAGG ||
+         plan.nodes[sh.bottom].kind == PK_PROJECTION ||
+         plan.nodes[sh.bottom].kind == PK_SELECTION)
+    sh.bottom = plan.nodes[sh.bottom].child;
+  return sh;
+}
+
+// the TopN's keys as columns of the aggregate's output, for the host sort
+// over the decoded groups; false when one is anything else
+static bool postSortKeysOf(const PPlan& plan, const PlanShape& sh,
+                           std::vector<std::pair<int, bool>>* keys) {
+  const PNode& topn = plan.nodes[sh.topn];
+  const PNode& agg = plan.nodes[sh.agg];
+  int aggWidth = (int)agg.exprs.size() + (int)agg.aggFuncs.size();
+  keys->clear();
+  for (size_t i = 0; i < topn.exprs.size(); i++) {
+    const PExpr& ke = plan.exprs[topn.exprs[i]];
+    if (ke.kind != EK_COLREF || ke.colIdx < 0 || ke.colIdx >= aggWidth)
+      return false;
+    keys->push_back({ke.colIdx, topn.keyDesc[i] != 0});
+  }
+  return true;
+}
+
+// device radix sort above a table of `types` columns (sortexec/sort.go:50,
+// 546; stable LSD passes over composed u64 keys): the TopN's keys, limit and
+// offset; `mustBe` is the complaint about a key that is no column of it
+static bool composeDevSortKeys(gx_exec* ex, const PNode& topn,
+                               const std::vector<int>& types,
+                               const char* mustBe) {
+  ex->devSortLimit = topn.limit;
+  ex->devSortOffset = topn.offset;
+  for (size_t i = 0; i < topn.exprs.size(); i++) {
+    const PExpr& ke = ex->plan.exprs[topn.exprs[i]];
+    if (ke.kind != EK_COLREF || ke.colIdx < 0 ||
+        ke.colIdx >= (int)types.size()) {
+      ex->err = mustBe;
+      return false;
+    }
+    gxp::SortKeyCompose k{};
+    k.col = ke.colIdx;
+    k.desc = topn.keyDesc[i] != 0;
+    int t = types[ke.colIdx];
+    if (t == GX_TYPE_I64) k.kind = 0;
+    else if (t == GX_TYPE_TIME) k.kind = 1;
+    else if (t == GX_TYPE_STRING) k.kind = 2;  // dense char, or ranked at run
+    else if (t == GX_TYPE_DECIMAL) k.kind = 3;
+    else if (t == GX_TYPE_F64) k.kind = 5;
+    else {
+      ex->err = "unsupported sort key type this round";
+      return false;
+    }
+    ex->devSortKeys.push_back(k);
+  }
+  return true;
+}
+
+// agg_stream_executor.go analog: semantics = grouped agg over a grouped
+// stream, emitted in stream order. MI355X-first implementation: the sort
+// below it is irrelevant to the aggregate VALUES, so run the fused hash
+// aggregation over the sort's input and emit ordered by the sort keys --
+// identical results, none of the sorted-input serialization.
+static int32_t compileStreamAgg(gx_exec* ex, int node) {
+  const PNode& sa = ex->plan.nodes[node];
+  const PNode& sortn = ex->plan.nodes[sa.child];
+  if (sortn.kind != PK_TOPN || sortn.limit >= 0) {
+    ex->err = "device streamagg expects a full-sort child this round";
+    return GX_ERR_INVALID;
+  }
+  // every sort key must be one of the group columns
+  for (size_t i = 0; i < sortn.exprs.size(); i++) {
+    const PExpr& ke = ex->plan.exprs[sortn.exprs[i]];
+    int found = -1;
+    for (size_t g = 0; g < sa.exprs.size(); g++) {
+      const PExpr& ge = ex->plan.exprs[sa.exprs[g]];
+      if (ke.kind == EK_COLREF && ge.kind == EK_COLREF &&
+          ke.colIdx == ge.colIdx)
+        found = (int)g;
+    }
+    if (found < 0) {
+      ex->err = "streamagg sort keys must be group columns";
+      return GX_ERR_INVALID;
+    }
+    ex->postSortKeys.push_back({found, sortn.keyDesc[i] != 0});
+  }
+  ex->postSort = true;
+  PNode agg;
+  agg.kind = PK_HASHAGG;
+  agg.child = sortn.child;
+  agg.aggMode = sa.aggMode;
+  agg.exprs = sa.exprs;
+  agg.aggFuncs = sa.aggFuncs;
+  agg.aggArgs = sa.aggArgs;
+  agg.aggFracs = sa.aggFracs;
+  ex->plan.nodes.push_back(agg);  // invalidates sa and sortn
+  return compileFused(ex, (int)ex->plan.nodes.size() - 1);
+}
+
+struct RouteList {
+  ExecKind kinds[3];
+  int n;
+  const char* failed;  // the error when the last compiler left none
+};
+
+// The routing table: which compilers may take the shape, in order.
+static RouteList routesFor(const PPlan& plan, const PlanShape& sh) {
+  using K = ExecKind;
+  static const char kPlanFailed[] = "plan compilation failed";
+  static const char kJoinFailed[] = "join plan compilation failed";
+  auto kindOf = [&](int n) { return plan.nodes[n].kind; };
+  const bool sorted = sh.topn >= 0;
+  const PNode& body = plan.nodes[sh.body];
+  if (sh.agg >= 0) {
+    // [TopN] <- [HAVING] <- HashAgg: the HAVING filter and the sort run on
+    // the host over the (small) decoded group rows (the reference sorts the
+    // agg output the same way -- Q1's final Sort, sortexec/sort.go)
+    if (!sorted)
+      return {{kindOf(sh.bottom) == PK_HASHJOIN ? K::AGG_OVER_JOIN : K::FUSED},
+              1, kPlanFailed};
+    // over a Source the join compilers have nothing to take
+    if (kindOf(sh.bottom) == PK_SOURCE) return {{K::FUSED}, 1, kPlanFailed};
+    std::vector<std::pair<int, bool>> keys;
+    if (!postSortKeysOf(plan, sh, &keys))
+      return {{K::JOIN_AGG}, 1, kPlanFailed};
+    // fused aggregation; else the Q3-class join-aggregate pipeline; else
+    // general aggregation over materialized joined rows
+    return {{K::FUSED, K::JOIN_AGG, K::AGG_OVER_JOIN}, 3, kPlanFailed};
+  }
+  switch (body.kind) {
+    case PK_SOURCE:  // bound table, sorted on device under a TopN
+      return {{K::BARE_SOURCE}, 1, kPlanFailed};
+    case PK_HASHJOIN:
+      return {{K::HASH_JOIN}, 1, kJoinFailed};
+    case PK_SELECTION:
+      // post-join conditions, or the standalone Selection (SelectionExec);
+      // under a TopN the materialized table feeds the device sort
+      if (kindOf(body.child) == PK_HASHJOIN)
+        return {{K::HASH_JOIN}, 1, kJoinFailed};
+      if (sorted && kindOf(body.child) == PK_SOURCE)
+        return {{K::SELECT}, 1, kJoinFailed};
+      if (!sorted && kindOf(skipFullSort(plan, body.child)) == PK_SOURCE)
+        return {{K::SELECT}, 1, kPlanFailed};
+      break;
+    case PK_HASHAGG:  // FINAL: the fusable ones are sh.agg
+      if (!sorted) return {{K::FINAL_HOST}, 1, kPlanFailed};
+      break;
+    case PK_STREAMAGG:
+      if (!sorted) return {{K::FUSED}, 1, kPlanFailed};
+      break;
+    case PK_PROJECTION:  // standalone Projection (ProjectionExec)
+      if (!sorted) return {{K::PROJECT}, 1, kPlanFailed};
+      break;
+    default:
+      break;
+  }
+  if (sorted) return {{K::JOIN_AGG}, 1, kJoinFailed};
+  return {{K::NONE}, 1,
+          "unsupported root plan node for the device engine this round"};
+}
+
+// Compiles ex's plan as route `k`; false with ex->err set when the route
+// refuses it (empty = the route list's text applies). *stop: a plan error
+// that no later route may paper over.
+static bool compileRoute(gx_exec* ex, const PlanShape& sh, ExecKind k,
+                         bool* stop) {
+  PPlan& plan = ex->plan;
+  *stop = true;
+  if (!composedOnlyAtRootProjection(ex)) return false;
+  if (sh.having >= 0 &&
+      !compileHaving(ex, plan.nodes[sh.having].exprs, plan.nodes[sh.agg]))
+    return false;
+  *stop = false;
+  // compilers append nodes to the plan: index it anew after one ran
+  const bool sorted = sh.topn >= 0;
+  switch (k) {
+    case ExecKind::FUSED:
+    case ExecKind::AGG_OVER_JOIN:
+      if (plan.nodes[sh.body].kind == PK_STREAMAGG)
+        return compileStreamAgg(ex, sh.body) == GX_OK;
+      if (sorted) {
+        if (!postSortKeysOf(plan, sh, &ex->postSortKeys)) {
+          ex->err = "sort keys must be aggregate output columns";
+          return false;
+        }
+        ex->postSort = true;
+        ex->postLimit = plan.nodes[sh.topn].limit;  // -1 = full sort
+        ex->postOffset = plan.nodes[sh.topn].offset;
+      }
+      return (k == ExecKind::FUSED ? compileFused(ex, sh.agg)
+                                   : compileAggOverJoin(ex, sh.agg)) == GX_OK;
+    case ExecKind::JOIN_AGG: {
+      bool ok = compileJoinAgg(ex, ex->root) == GX_OK;
+      *stop = ex->jaLikeRejected;
+      return ok;
+    }
+    case ExecKind::FINAL_HOST: {
+      const PNode& agg = plan.nodes[sh.body];
+      if (plan.nodes[agg.child].kind != PK_SOURCE) {
+        ex->err = "FINAL agg child must be a bound source";
+        return false;
+      }
+      for (int f : agg.aggFuncs)
+        if (f >= GX_AGG_COUNT_DISTINCT) {
+          ex->err = "DISTINCT aggregates support COMPLETE mode only";
+          return false;
+        }
+      ex->sourceNode = agg.child;
+      return true;
+    }
+    case ExecKind::BARE_SOURCE: {
+      const PNode& src = plan.nodes[sh.body];
+      ex->sourceNode = sh.body;
+      setTableMeta(&ex->desc.table, src.colTypes, src.colFracs);
+      return !sorted ||
+             composeDevSortKeys(ex, plan.nodes[sh.topn], src.colTypes,
+                                "sort keys must be source columns");
+    }
+    case ExecKind::HASH_JOIN:
+      if (compileHashJoinTree(ex, sh.body) != GX_OK) return false;
+      return !sorted ||
+             composeDevSortKeys(ex, plan.nodes[sh.topn],
+                                ex->joinStages.back().types,
+                                "sort keys must be join output columns");
+    case ExecKind::SELECT:
+      if (compileSelect(ex, sh.body) != GX_OK) return false;
+      return !sorted ||
+             composeDevSortKeys(ex, plan.nodes[sh.topn], ex->selStage.types,
+                                "sort keys must be join output columns");
+    case ExecKind::PROJECT:
+      return compileProject(ex, sh.body) == GX_OK;
+    case ExecKind::NONE:  // no route: only the checks every plan gets
+      break;
+  }
+  return false;
+}
+
 gx_exec* gx_build(gx_pb* pb, int32_t root, int32_t device) {
   if (!pb || root < 0 || root >= (int32_t)pb->plan.nodes.size()) return nullptr;
-  auto* ex = new gx_exec();
-  ex->plan = pb->plan;
-  ex->root = root;
-  ex->device = device;
-  if (!composedOnlyAtRootProjection(ex)) return ex;
-  const PNode& rn = ex->plan.nodes[root];
-  if (rn.kind == PK_HASHAGG && rn.aggMode == GX_AGG_MODE_FINAL) {
-    if (ex->plan.nodes[rn.child].kind != PK_SOURCE) {
-      ex->err = "FINAL agg child must be a bound source";
+  const PlanShape sh = classifyPlan(pb->plan, root);
+  const RouteList routes = routesFor(pb->plan, sh);
+  gx_exec* ex = nullptr;
+  bool stop = false;
+  for (int i = 0; i < routes.n && !stop; i++) {
+    delete ex;  // a refused attempt: nothing of it reaches the next one
+    ex = new gx_exec();
+    ex->plan = pb->plan;
+    ex->root = root;
+    ex->device = device;
+    if (compileRoute(ex, sh, routes.kinds[i], &stop)) {
+      ex->kind = routes.kinds[i];
       return ex;
     }
-    for (int f : rn.aggFuncs)
-      if (f >= GX_AGG_COUNT_DISTINCT) {
-        ex->err = "DISTINCT aggregates support COMPLETE mode only";
-        return ex;
-      }
-    ex->isFinalHost = true;
-    ex->sourceNode = rn.child;
-  } else if (rn.kind == PK_SELECTION &&
-             ex->plan.nodes[rn.child].kind == PK_HASHAGG &&
-             ex->plan.nodes[rn.child].aggMode != GX_AGG_MODE_FINAL) {
-    // HAVING: a Selection over the aggregate's output — run the fused
-    // aggregation and filter the (small) decoded group rows on the host
-    // (the reference evaluates HAVING the same way, above the agg)
-    if (!compileHaving(ex, rn.exprs, ex->plan.nodes[rn.child])) return ex;
-    int aggRoot = rn.child;
-    int node = aggRoot;
-    while (ex->plan.nodes[node].kind == PK_HASHAGG ||
-           ex->plan.nodes[node].kind == PK_PROJECTION ||
-           ex->plan.nodes[node].kind == PK_SELECTION)
-      node = ex->plan.nodes[node].child;
-    int saved = ex->root;
-    ex->root = aggRoot;
-    int32_t rc = ex->plan.nodes[node].kind == PK_HASHJOIN
-                     ? compileAggOverJoin(ex, aggRoot)
-                     : compileFused(ex);
-    ex->root = saved;
-    if (rc != GX_OK && ex->err.empty()) ex->err = "plan compilation failed";
-    (void)rc;
-  } else if (rn.kind == PK_HASHAGG) {
-    // bottom of the subtree: a Source (fused pipeline) or a HashJoin
-    // (aggregation over materialized joined rows)
-    int node = root;
-    while (ex->plan.nodes[node].kind == PK_HASHAGG ||
-           ex->plan.nodes[node].kind == PK_PROJECTION ||
-           ex->plan.nodes[node].kind == PK_SELECTION)
-      node = ex->plan.nodes[node].child;
-    int32_t rc = ex->plan.nodes[node].kind == PK_HASHJOIN
-                     ? compileAggOverJoin(ex, root)
-                     : compileFused(ex);
-    if (rc != GX_OK && ex->err.empty()) ex->err = "plan compilation failed";
-    (void)rc;
-  } else if (rn.kind == PK_TOPN &&
-             ((ex->plan.nodes[rn.child].kind == PK_HASHAGG &&
-               ex->plan.nodes[rn.child].aggMode != GX_AGG_MODE_FINAL) ||
-              (ex->plan.nodes[rn.child].kind == PK_SELECTION &&
-               ex->plan.nodes[ex->plan.nodes[rn.child].child].kind ==
-                   PK_HASHAGG &&
-               ex->plan.nodes[ex->plan.nodes[rn.child].child].aggMode !=
-                   GX_AGG_MODE_FINAL))) {
-    // ORDER BY / TopN over a fusable aggregation, optionally through a
-    // HAVING Selection: run the fused kernel, filter + sort the (small)
-    // group output on the host (the reference sorts the agg output the
-    // same way — Q1's final Sort, sortexec/sort.go)
-    int aggRoot = rn.child;
-    if (ex->plan.nodes[aggRoot].kind == PK_SELECTION) {
-      const std::vector<int>& conds = ex->plan.nodes[aggRoot].exprs;
-      aggRoot = ex->plan.nodes[aggRoot].child;
-      if (!compileHaving(ex, conds, ex->plan.nodes[aggRoot])) return ex;
-    }
-    int aggWidth = (int)ex->plan.nodes[aggRoot].exprs.size() +
-                   (int)ex->plan.nodes[aggRoot].aggFuncs.size();
-    bool ok = true;
-    for (size_t i = 0; i < rn.exprs.size(); i++) {
-      const PExpr& ke = ex->plan.exprs[rn.exprs[i]];
-      if (ke.kind != EK_COLREF || ke.colIdx < 0 || ke.colIdx >= aggWidth) {
-        ex->err = "sort keys must be aggregate output columns";
-        ok = false;
-        break;
-      }
-      ex->postSortKeys.push_back({ke.colIdx, rn.keyDesc[i] != 0});
-    }
-    if (ok) {
-      ex->postSort = true;
-      ex->postLimit = rn.limit;  // -1 = full sort
-      ex->postOffset = rn.offset;
-      int saved = ex->root;
-      ex->root = aggRoot;
-      int32_t rc = compileFused(ex);
-      ex->root = saved;
-      if (rc != GX_OK) {
-        // not a fusable aggregation subtree (e.g. Q3's agg-over-join):
-        // reset and try the join-aggregate pipeline
-        std::vector<std::pair<int, bool>> savedKeys = ex->postSortKeys;
-        ex->err.clear();
-        ex->isFused = false;
-        ex->postSort = false;
-        ex->postSortKeys.clear();
-        ex->desc = gxp::FusedQueryDesc{};
-        ex->projRegs.clear();
-        rc = compileJoinAgg(ex);
-        if (rc != GX_OK && ex->jaLikeRejected) {
-          ex->postSortKeys.clear();
-        } else if (rc != GX_OK) {
-          // last resort: general aggregation over materialized joined rows
-          // + host post-sort (keys already validated as agg output columns)
-          ex->err.clear();
-          ex->desc = gxp::FusedQueryDesc{};
-          ex->projRegs.clear();
-          ex->postSort = true;
-          ex->postSortKeys = savedKeys;
-          ex->postLimit = rn.limit;
-          ex->postOffset = rn.offset;
-          rc = compileAggOverJoin(ex, aggRoot);
-          if (rc != GX_OK) {
-            ex->postSort = false;
-            ex->postSortKeys.clear();
-            if (ex->err.empty()) ex->err = "plan compilation failed";
-          }
-        }
-      }
-    } else {
-      ex->err.clear();
-      int32_t rc = compileJoinAgg(ex);
-      if (rc != GX_OK && ex->err.empty()) ex->err = "plan compilation failed";
-    }
-  } else if (rn.kind == PK_STREAMAGG) {
-    // agg_stream_executor.go analog: semantics = grouped agg over a grouped
-    // stream, emitted in stream order. MI355X-first implementation: the
-    // sort below it is irrelevant to the aggregate VALUES, so run the fused
-    // hash aggregation over the sort's input and emit ordered by the sort
-    // keys -- identical results, none of the sorted-input serialization.
-    const PNode* sortn = &ex->plan.nodes[rn.child];
-    if (sortn->kind != PK_TOPN || sortn->limit >= 0) {
-      ex->err = "device streamagg expects a full-sort child this round";
-      return ex;
-    }
-    // every sort key must be one of the group columns
-    std::vector<std::pair<int, bool>> orderKeys;
-    bool ok = true;
-    for (size_t i = 0; i < sortn->exprs.size() && ok; i++) {
-      const PExpr& ke = ex->plan.exprs[sortn->exprs[i]];
-      int found = -1;
-      for (size_t g = 0; g < rn.exprs.size(); g++) {
-        const PExpr& ge = ex->plan.exprs[rn.exprs[g]];
-        if (ke.kind == EK_COLREF && ge.kind == EK_COLREF &&
-            ke.colIdx == ge.colIdx)
-          found = (int)g;
-      }
-      if (found < 0) {
-        ex->err = "streamagg sort keys must be group columns";
-        ok = false;
-      } else {
-        orderKeys.push_back({found, sortn->keyDesc[i] != 0});
-      }
-    }
-    if (ok) {
-      PNode agg;
-      agg.kind = PK_HASHAGG;
-      agg.child = sortn->child;
-      agg.aggMode = rn.aggMode;
-      agg.exprs = rn.exprs;
-      agg.aggFuncs = rn.aggFuncs;
-      agg.aggArgs = rn.aggArgs;
-      agg.aggFracs = rn.aggFracs;
-      ex->plan.nodes.push_back(agg);
-      int saved = ex->root;
-      ex->root = (int)ex->plan.nodes.size() - 1;
-      ex->postSort = true;
-      ex->postSortKeys = orderKeys;
-      ex->postLimit = -1;
-      ex->postOffset = 0;
-      int32_t rc = compileFused(ex);
-      ex->root = saved;
-      if (rc != GX_OK && ex->err.empty()) ex->err = "plan compilation failed";
-    }
-  } else if (rn.kind == PK_TOPN &&
-             ex->plan.nodes[rn.child].kind == PK_SOURCE) {
-    // full ORDER BY / TopN directly over a source table: device radix sort
-    // (sortexec/sort.go:50,546; stable LSD passes over composed u64 keys)
-    const PNode& srcn = ex->plan.nodes[rn.child];
-    ex->isBareSource = true;
-    ex->sourceNode = rn.child;
-    ex->desc.table.nCols = (int)srcn.colTypes.size();
-    for (size_t c = 0; c < srcn.colTypes.size(); c++)
-      setDevColMeta(&ex->desc.table.cols[c], srcn.colTypes[c], srcn.colFracs[c]);
-    ex->devSortLimit = rn.limit;
-    ex->devSortOffset = rn.offset;
-    bool ok = true;
-    for (size_t i = 0; i < rn.exprs.size(); i++) {
-      const PExpr& ke = ex->plan.exprs[rn.exprs[i]];
-      if (ke.kind != EK_COLREF || ke.colIdx < 0 ||
-          ke.colIdx >= (int)srcn.colTypes.size()) {
-        ex->err = "sort keys must be source columns";
-        ok = false;
-        break;
-      }
-      gxp::SortKeyCompose k{};
-      k.col = ke.colIdx;
-      k.desc = rn.keyDesc[i] != 0;
-      int t = srcn.colTypes[ke.colIdx];
-      if (t == GX_TYPE_I64) k.kind = 0;
-      else if (t == GX_TYPE_TIME) k.kind = 1;
-      else if (t == GX_TYPE_STRING) k.kind = 2;  // dense char, or ranked at run
-      else if (t == GX_TYPE_DECIMAL) k.kind = 3;
-      else if (t == GX_TYPE_F64) k.kind = 5;
-      else {
-        ex->err = "unsupported sort key type this round";
-        ok = false;
-        break;
-      }
-      ex->devSortKeys.push_back(k);
-    }
-    (void)ok;
-  } else if (rn.kind == PK_TOPN &&
-             ex->plan.nodes[rn.child].kind != PK_HASHJOIN &&
-             !(ex->plan.nodes[rn.child].kind == PK_SELECTION &&
-               (ex->plan.nodes[ex->plan.nodes[rn.child].child].kind ==
-                    PK_HASHJOIN ||
-                ex->plan.nodes[ex->plan.nodes[rn.child].child].kind ==
-                    PK_SOURCE))) {
-    int32_t rc = compileJoinAgg(ex);
-    if (rc != GX_OK && ex->err.empty()) ex->err = "join plan compilation failed";
-    (void)rc;
-  } else if (rn.kind == PK_SOURCE) {
-    ex->isBareSource = true;
-    ex->sourceNode = root;
-    ex->desc.table.nCols = (int)rn.colTypes.size();
-    for (size_t c = 0; c < rn.colTypes.size(); c++)
-      setDevColMeta(&ex->desc.table.cols[c], rn.colTypes[c], rn.colFracs[c]);
-  } else if (rn.kind == PK_HASHJOIN ||
-             (rn.kind == PK_SELECTION &&
-              ex->plan.nodes[rn.child].kind == PK_HASHJOIN)) {
-    int32_t rc = compileHashJoinTree(ex, root);
-    if (rc != GX_OK && ex->err.empty()) ex->err = "join plan compilation failed";
-    (void)rc;
-  } else if (rn.kind == PK_SELECTION &&
-             ex->plan.nodes[skipFullSort(ex, rn.child)].kind == PK_SOURCE) {
-    // standalone Selection (SelectionExec): survivors compacted on device
-    int32_t rc = compileSelect(ex, root);
-    if (rc != GX_OK && ex->err.empty()) ex->err = "plan compilation failed";
-    (void)rc;
-  } else if (rn.kind == PK_PROJECTION) {
-    // standalone Projection (ProjectionExec): computed columns materialize
-    int32_t rc = compileProject(ex);
-    if (rc != GX_OK && ex->err.empty()) ex->err = "plan compilation failed";
-    (void)rc;
-  } else if (rn.kind == PK_TOPN &&
-             (ex->plan.nodes[rn.child].kind == PK_HASHJOIN ||
-              (ex->plan.nodes[rn.child].kind == PK_SELECTION &&
-               (ex->plan.nodes[ex->plan.nodes[rn.child].child].kind ==
-                    PK_HASHJOIN ||
-                ex->plan.nodes[ex->plan.nodes[rn.child].child].kind ==
-                    PK_SOURCE)))) {
-    // ORDER BY / TopN over joined or filtered rows: materialize the device
-    // table (join stages or selection compaction), then the device radix
-    // sort over it (sortexec/sort.go)
-    const PNode& cn = ex->plan.nodes[rn.child];
-    bool selOverSource =
-        cn.kind == PK_SELECTION &&
-        ex->plan.nodes[cn.child].kind == PK_SOURCE;
-    int32_t rc = selOverSource ? compileSelect(ex, rn.child)
-                               : compileHashJoinTree(ex, rn.child);
-    if (rc != GX_OK) {
-      if (ex->err.empty()) ex->err = "join plan compilation failed";
-      return ex;
-    }
-    ex->devSortLimit = rn.limit;
-    ex->devSortOffset = rn.offset;
-    for (size_t i = 0; i < rn.exprs.size(); i++) {
-      const PExpr& ke = ex->plan.exprs[rn.exprs[i]];
-      if (ke.kind != EK_COLREF || ke.colIdx < 0 ||
-          ke.colIdx >= ex->desc.table.nCols) {
-        ex->err = "sort keys must be join output columns";
-        return ex;
-      }
-      gxp::SortKeyCompose k{};
-      k.col = ke.colIdx;
-      k.desc = rn.keyDesc[i] != 0;
-      int t = ex->desc.table.cols[ke.colIdx].type;
-      if (t == GX_TYPE_I64) k.kind = 0;
-      else if (t == GX_TYPE_TIME) k.kind = 1;
-      else if (t == GX_TYPE_STRING) k.kind = 2;  // dense char, or ranked at run
-      else if (t == GX_TYPE_DECIMAL) k.kind = 3;
-      else if (t == GX_TYPE_F64) k.kind = 5;
-      else {
-        ex->err = "unsupported sort key type this round";
-        return ex;
-      }
-      ex->devSortKeys.push_back(k);
-    }
-  } else {
-    ex->err = "unsupported root plan node for the device engine this round";
   }
+  if (ex->err.empty()) ex->err = routes.failed;
   return ex;
 }
 
@@ -6845,8 +6833,7 @@ int32_t gx_bind_tpch(gx_exec* ex, int32_t source_node, int32_t table,
 int32_t gx_open(gx_exec* ex) {
   if (!ex) return GX_ERR_INVALID;
   if (!ex->err.empty()) return GX_ERR_INVALID;
-  if (!ex->isFused && !ex->isFinalHost && !ex->isBareSource && !ex->isJoinAgg &&
-      !ex->isHashJoin && !ex->isSelect && !ex->isProject) {
+  if (ex->kind == ExecKind::NONE) {
     ex->err = "plan not executable";
     return GX_ERR_INVALID;
   }
@@ -6856,7 +6843,9 @@ int32_t gx_open(gx_exec* ex) {
   ex->resultRows.clear();
   // join/select/project re-runs rebuild desc.table from scratch (beginRun
   // frees the previous run's buffers), so a sort above them must re-run too
-  if (ex->isHashJoin || ex->isSelect || ex->isProject) ex->devSorted = false;
+  if (ex->kind == ExecKind::HASH_JOIN || ex->kind == ExecKind::SELECT ||
+      ex->kind == ExecKind::PROJECT)
+    ex->devSorted = false;
   // a bare source keeps its sorted (or limited) table, cut to offset + limit:
   // emission restarts at the slice's first row, the sort does not rerun
   if (ex->devSorted) ex->srcPos = ex->sliceStart;
@@ -6869,98 +6858,72 @@ int32_t gx_open(gx_exec* ex) {
   return GX_OK;
 }
 
-int32_t gx_next(gx_exec* ex, gx_chunk* out, int32_t* rows_out) {
-  if (!ex || !ex->opened) return GX_ERR_INVALID;
-  if (ex->isBareSource) return emitSourceChunk(ex, out, rows_out);
-  if (ex->isProject) {
-    if (!ex->ranQuery) {
-      int32_t rc = runProject(ex);
-      if (rc) {
-        *rows_out = 0;
-        return rc;
-      }
-      ex->ranQuery = true;
-    }
-    return emitTableChunk(ex, out, rows_out);
-  }
-  if (ex->isSelect) {
-    if (!ex->ranQuery) {
-      int32_t rc = runSelect(ex);
-      if (rc) {
-        *rows_out = 0;
-        return rc;
-      }
-      ex->ranQuery = true;
-    }
-    if (!ex->devSortKeys.empty() && !ex->devSorted) {
-      int32_t rc = runDeviceSort(ex);
-      if (rc) {
-        *rows_out = 0;
-        return rc;
-      }
-    }
-    applyBareLimit(ex);
-    return emitTableChunk(ex, out, rows_out);
-  }
-  if (ex->isHashJoin) {
-    if (!ex->ranQuery) {
-      int32_t rc = runHashJoin(ex);
-      if (rc) {
-        *rows_out = 0;
-        return rc;
-      }
-      ex->ranQuery = true;
-    }
-    if (!ex->devSortKeys.empty() && !ex->devSorted) {
-      if (ex->joinSpill) {
-        ex->err = "ORDER BY over an out-of-core join unsupported this round";
-        *rows_out = 0;
-        return GX_ERR_INVALID;
-      }
-      int32_t rc = runDeviceSort(ex);
-      if (rc) {
-        *rows_out = 0;
-        return rc;
-      }
-    }
-    if (ex->devSortKeys.empty() && !ex->devSorted && ex->joinSpill &&
-        (ex->devSortLimit >= 0 || ex->devSortOffset > 0)) {
-      ex->err = "LIMIT over an out-of-core join unsupported this round";
-      *rows_out = 0;
-      return GX_ERR_INVALID;
-    }
-    applyBareLimit(ex);
-    int32_t rc = emitTableChunk(ex, out, rows_out);
-    // out-of-core: stream the next partitions' outputs
-    while (rc == GX_OK && *rows_out == 0 && ex->joinSpill &&
-           ex->joinSpillCur < (int)ex->spillB.size()) {
-      rc = joinSpillAdvance(ex);
-      if (rc || ex->joinSpillCur >= (int)ex->spillB.size()) break;
-      rc = emitTableChunk(ex, out, rows_out);
-    }
-    return rc;
-  }
-  if (!ex->ranQuery) {
-    int32_t rc;
-    if (ex->aggOverJoin) {
+// the query itself, once per open
+static int32_t runQuery(gx_exec* ex) {
+  switch (ex->kind) {
+    case ExecKind::FUSED: return runFused(ex);
+    case ExecKind::AGG_OVER_JOIN: {
       // materialize the joined rows, finish the fused bind over that table,
       // then aggregate (materializeDevice no-ops: runHashJoin set
       // deviceReady)
-      rc = runHashJoin(ex);
+      int32_t rc = runHashJoin(ex);
       if (rc == GX_OK) rc = finalizeFusedBind(ex);
       if (rc == GX_OK) rc = runFused(ex);
-    } else {
-      rc = ex->isFinalHost ? runFinalHost(ex)
-           : ex->isJoinAgg ? runJoinAgg(ex)
-                           : runFused(ex);
-    }
-    if (rc) {
-      *rows_out = 0;
       return rc;
     }
+    case ExecKind::FINAL_HOST: return runFinalHost(ex);
+    case ExecKind::JOIN_AGG: return runJoinAgg(ex);
+    case ExecKind::HASH_JOIN: return runHashJoin(ex);
+    case ExecKind::SELECT: return runSelect(ex);
+    case ExecKind::PROJECT: return runProject(ex);
+    case ExecKind::BARE_SOURCE:  // materializes as it emits
+    case ExecKind::NONE: break;
+  }
+  return GX_OK;
+}
+
+int32_t gx_next(gx_exec* ex, gx_chunk* out, int32_t* rows_out) {
+  if (!ex || !ex->opened) return GX_ERR_INVALID;
+  if (ex->kind == ExecKind::BARE_SOURCE)
+    return emitSourceChunk(ex, out, rows_out);
+  auto fail = [&](int32_t rc) {
+    *rows_out = 0;
+    return rc;
+  };
+  if (!ex->ranQuery) {
+    int32_t rc = runQuery(ex);
+    if (rc) return fail(rc);
     ex->ranQuery = true;
   }
-  return gxp::emitRows(ex->resultRows, &ex->emitPos, out, rows_out, &ex->err);
+  if (ex->kind != ExecKind::HASH_JOIN && ex->kind != ExecKind::SELECT &&
+      ex->kind != ExecKind::PROJECT)
+    return gxp::emitRows(ex->resultRows, &ex->emitPos, out, rows_out, &ex->err);
+  // a device table: sort it if keys are pending, cut it to the limit, emit;
+  // only a HASH_JOIN spills (runHashJoin), one partition's output at a time
+  const bool spill = ex->kind == ExecKind::HASH_JOIN && ex->joinSpill;
+  if (!ex->devSortKeys.empty() && !ex->devSorted) {
+    if (spill) {
+      ex->err = "ORDER BY over an out-of-core join unsupported this round";
+      return fail(GX_ERR_INVALID);
+    }
+    int32_t rc = runDeviceSort(ex);
+    if (rc) return fail(rc);
+  }
+  if (spill && ex->devSortKeys.empty() && !ex->devSorted &&
+      (ex->devSortLimit >= 0 || ex->devSortOffset > 0)) {
+    ex->err = "LIMIT over an out-of-core join unsupported this round";
+    return fail(GX_ERR_INVALID);
+  }
+  applyBareLimit(ex);
+  int32_t rc = emitTableChunk(ex, out, rows_out);
+  // out-of-core: stream the next partitions' outputs
+  while (spill && rc == GX_OK && *rows_out == 0 &&
+         ex->joinSpillCur < (int)ex->spillB.size()) {
+    rc = joinSpillAdvance(ex);
+    if (rc || ex->joinSpillCur >= (int)ex->spillB.size()) break;
+    rc = emitTableChunk(ex, out, rows_out);
+  }
+  return rc;
 }
 
 int32_t gx_close(gx_exec* ex) {
@@ -6993,13 +6956,13 @@ const char* gx_debug_vm_program(gx_exec* ex) {
   static std::string s;
   s.clear();
   if (!ex) return "";
-  if (ex->isJoinAgg) {
+  if (ex->kind == ExecKind::JOIN_AGG) {
     int nLoads = 0;  // the probe kernel does not store it: leading loads
     while (nLoads < ex->ja.nIns && (ex->ja.ins[nLoads].op == gxp::VM_LOAD_DEC ||
                                     ex->ja.ins[nLoads].op == gxp::VM_LOAD_I64))
       nLoads++;
     dumpVmProgram(s, "probe", ex->ja, nLoads, -1, ex->ja.fetch, ex->ja.nFetch, 0);
-  } else if (ex->isProject) {
+  } else if (ex->kind == ExecKind::PROJECT) {
     dumpVmProgram(s, "projection", ex->pd, 0, -1, nullptr, 0, ex->pd.nLikePats);
     // composed string programs: a section of their own, only when present
     for (int ci = 0; ci < ex->pd.nCat; ci++) {
@@ -7024,7 +6987,7 @@ const char* gx_debug_vm_program(gx_exec* ex) {
       }
     }
     if (ex->pd.nCat > 0) s += "strcatPool=" + std::to_string(ex->pd.catPoolLen) + "\n";
-  } else if (ex->isFused) {
+  } else if (ex->usesFusedDesc()) {
     dumpVmProgram(s, "fused", ex->desc, ex->desc.nLoadIns, ex->desc.nVmRegs,
                   ex->desc.fetch, ex->desc.nFetch, ex->desc.nLikePats);
   } else {
@@ -7039,7 +7002,7 @@ const char* gx_debug_vm_program(gx_exec* ex) {
 int32_t gx_debug_strcat_eval(gx_exec* ex, int32_t out_col, const gx_chunk* in,
                              gx_col* out) {
   if (!ex || !in || !out) return GX_ERR_INVALID;
-  if (!ex->isProject || out_col < 0 || out_col >= (int)ex->projOutCat.size() ||
+  if (ex->kind != ExecKind::PROJECT || out_col < 0 || out_col >= (int)ex->projOutCat.size() ||
       ex->projOutCat[out_col] < 0) {
     ex->err = "gx_debug_strcat_eval: not a composed string output";
     return GX_ERR_INVALID;
@@ -7106,7 +7069,8 @@ int32_t gx_debug_dec_units_cols(gx_exec* ex) {
 int32_t gx_debug_dec_units_width(gx_exec* ex, int32_t col) {
   if (!ex || col < 0 || col >= gxp::kMaxCols) return 0;
   const gxp::DevCol& c =
-      (ex->isJoinAgg ? ex->ja.probe : ex->desc.table).cols[col];
+      (ex->kind == ExecKind::JOIN_AGG ? ex->ja.probe : ex->desc.table)
+          .cols[col];
   return c.units ? c.unitsWidth : 0;
 }
 
@@ -7129,7 +7093,7 @@ int32_t gx_debug_result_compact(gx_exec* ex) {
 
 // debug: group slots of the replicated LDS table for this plan (0 = none)
 int32_t gx_debug_lds_repl_slots(gx_exec* ex) {
-  return ex && ex->isFused ? gxjit::replSlots(ex->desc) : 0;
+  return ex && ex->usesFusedDesc() ? gxjit::replSlots(ex->desc) : 0;
 }
 
 double gx_last_kernel_ms(gx_exec* ex) { return ex ? ex->lastKernelMs : 0; }
